@@ -11,7 +11,16 @@ Default workload (config 4, per GPU): 4096 envs x 64 vehicles, Kinematics 15x7
 random-seeded scenes and uniformly random ego actions (pre-drawn on the device).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f64|f32] [--config 1..6] [--auto-reset] [--strong]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step,
+the workload).  --full adds what takes runs of its own: the ``roofline`` object (the fused launch
+timed with HIP events on extra steps after the timed ones, the committed PMC profile) and the
+``cpu_baseline`` on the host cores (--no-cpu-baseline leaves that one out).
+--dump-outputs DIR: after the timed steps, what the last timed env.step returned (obs, reward,
+terminated, truncated, the info tensors; config 5 also the policy's actions) as DIR/<name>.npy,
+float32 or float64, at most 64 MB (a fixed seeded sample of the envs where an array is larger).
 
 --gpus N > 1 without a torch.distributed.run environment: this process touches no GPU, starts
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py`` as a CHILD process (one rank
@@ -232,6 +241,59 @@ def read_pmc(dtype: str, cfg_id: int) -> tuple[dict | None, str]:
     return e, f"profiles/pmc_traffic.json ({e.get('profile', '?')}, libttrl_mi355x.so {e['so_sha16']})"
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes of .npy payload one run may write (all ranks together)
+
+
+def step_outputs(last, actions=None) -> dict:
+    """{name: device tensor} of what the last timed step returned: env.step's (obs, reward,
+    terminated, truncated, info) or StepGraph.replay's four, and the policy's actions if given."""
+    obs, reward, terminated, truncated, *rest = last
+    out = {"obs": obs, "reward": reward, "terminated": terminated, "truncated": truncated}
+    for k, v in (rest[0] if rest else {}).items():
+        if k == "action":  # the caller's own input
+            continue
+        for kk, vv in (v.items() if isinstance(v, dict) else [(None, v)]):
+            if hasattr(vv, "detach"):
+                out[f"info_{k}" if kk is None else f"info_{k}_{kk}"] = vv
+    if actions is not None:
+        out["actions"] = actions
+    return out
+
+
+def dump_outputs(path: str, tensors: dict, rank: int = 0, world: int = 1) -> dict:
+    """Write every tensor as path/<name>.npy (rank r of several: <name>.rank<r>.npy): floating
+    tensors keep float32 / float64, bool and small integers go to float32, wide integers to float64.
+    If the arrays exceed the byte budget, those above 1 MB keep the same fixed, seeded (sorted) sample
+    of their rows (envs), written to path/sample_rows.npy too.  Returns {name: shape written}."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64 if t.dtype in (torch.int32, torch.int64) else torch.float32)
+        arrays[name] = t
+    budget = DUMP_BUDGET // world - 256 * (len(arrays) + 1)  # less the .npy headers
+    size = lambda t: t.numel() * t.element_size()  # noqa: E731
+    big = {n: t for n, t in arrays.items() if size(t) > 1_000_000 and t.dim() >= 1}
+    small = sum(size(t) for n, t in arrays.items() if n not in big)
+    shapes = {}
+    suffix = f".rank{rank}" if world > 1 else ""
+    if big and small + sum(size(t) for t in big.values()) > budget:
+        rows = min(t.shape[0] for t in big.values())
+        per_row = sum(size(t) // t.shape[0] for t in big.values())
+        keep = max(1, min(rows, (budget - small - 8 * rows) // per_row))
+        idx = np.sort(np.random.default_rng(20240607).choice(rows, size=keep, replace=False))
+        sel = torch.from_numpy(idx).to(next(iter(big.values())).device)
+        arrays.update({n: t.index_select(0, sel) for n, t in big.items()})
+        np.save(os.path.join(path, f"sample_rows{suffix}.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.cpu().numpy())
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def launch_ranks(n: int, argv: list) -> int:
     """``bench.py --gpus n`` outside torch.distributed.run: run the ranks as a child
     ``torch.distributed.run`` job on 127.0.0.1 (a subprocess, never an exec: this process has not
@@ -318,7 +380,11 @@ def main():
     ap.add_argument("--config", type=int, default=4, choices=[1, 2, 3, 4, 5, 6])
     ap.add_argument("--auto-reset", action="store_true",
                     help="highway envs restart on termination inside env.step (the RL rollout mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (launch times on extra steps, the PMC profile) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--graph", action="store_true",
                     help="replay each step as one captured HIP graph (policy + env.step for config 5)")
@@ -331,6 +397,8 @@ def main():
         args.warmup = 10 if args.config == 6 else 3
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from topotrafficrl_amd import sharding
     rank, local, world = sharding.world()
@@ -400,18 +468,22 @@ def main():
         from topotrafficrl_amd.graph import StepGraph
         sg = StepGraph(env, obs, policy)
 
+    last = None  # what the latest step returned, and the policy's actions that went into it
+
     def one_step(t):
-        nonlocal obs
+        nonlocal obs, last
         if sg is not None:
             if policy is None:
                 sg.set_actions(acts[t])
-            sg.replay()
+            last = (sg.replay(), sg.actions if policy is not None else None)
             return
         a = policy.act(obs, t, dtype=torch.int32) if policy is not None else acts[t]
         obs, rew, term, trunc, info = env.step(a)
+        last = ((obs, rew, term, trunc, info), a if policy is not None else None)
 
     kern_warm = []
-    if sg is not None:  # graph replays cannot carry timing events: time the fused kernel on untimed launches
+    # --full: graph replays cannot carry timing events, so time the fused kernel on untimed launches
+    if sg is not None and args.full:
         road = env.road
         for _ in range(3):
             snap = env.state.clone()
@@ -440,7 +512,8 @@ def main():
     # there (tools/gap_ab.py, profiles/r06/r06l_event_markers.txt), and bracketing only every 4th
     # timed launch overstated the launch by 6 % against rocprofv3's trace of the same process
     # (profiles/r06/r06o_trace_agreement.txt: the marker before a bracketed launch behind a bare one
-    # also times the dispatch behind it).
+    # also times the dispatch behind it).  Only with --full: a plain run installs no wrapper and
+    # runs no step beyond the timed ones.
     N_EV, N_SETTLE = min(args.steps, 20), 3
     from topotrafficrl_amd.road import BatchedRoad
     orig_sim, orig_env_step, orig_ix_step = BatchedRoad.simulate, BatchedRoad.env_step, BatchedRoad.ix_env_step
@@ -460,8 +533,9 @@ def main():
             return r
         return wrapper
 
-    BatchedRoad.simulate, BatchedRoad.env_step = timed(orig_sim), timed(orig_env_step)
-    BatchedRoad.ix_env_step = timed(orig_ix_step)
+    if args.full:
+        BatchedRoad.simulate, BatchedRoad.env_step = timed(orig_sim), timed(orig_env_step)
+        BatchedRoad.ix_env_step = timed(orig_ix_step)
     # config 3: the OccupancyGrid launch (the path's HBM-bound kernel) timed the same way
     from topotrafficrl_amd.observation import BatchedOccupancyGridObservation
     orig_grid = BatchedOccupancyGridObservation.observe
@@ -478,7 +552,8 @@ def main():
         grid_launches.append((s, e))
         return r
 
-    BatchedOccupancyGridObservation.observe = timed_grid
+    if args.full:
+        BatchedOccupancyGridObservation.observe = timed_grid
     t0 = time.perf_counter()
     for t in range(args.warmup, args.warmup + args.steps):
         one_step(t)
@@ -489,7 +564,10 @@ def main():
     elapsed = time.perf_counter() - t0
     if ix:  # the counter holds the tails of the timed steps: the last one counts the step after them
         live_steps = live0 + int(live.item()) - int((env.state["kind"] != 0).sum())
-    if sg is None:  # untimed: the launch-time steps (actions reused from the start of the table)
+    dumped = None
+    if args.dump_outputs:  # the last timed step's results, before anything else steps the envs
+        dumped = dump_outputs(args.dump_outputs, step_outputs(*last), rank, world)
+    if sg is None and args.full:  # untimed: the launch-time steps (actions reused from the start of the table)
         for u in range(N_SETTLE + N_EV):
             sample[0] = u >= N_SETTLE
             if sample[0]:
@@ -504,33 +582,12 @@ def main():
         s0 = recs[0][0]
         return max(s0.elapsed_time(e) for _, e in recs) - min(s0.elapsed_time(s) for s, _ in recs)
 
-    kern_ms = float(np.mean(kern_warm)) if sg is not None else float(np.mean([span(r) for r in launches if r]))
     elapsed = sharding.max_over_ranks(elapsed, device=None if shared else dev)
 
     veh_steps = global_envs * N * 15 * args.steps
     if ix:  # live vehicles, not slots, summed over the ranks
         veh_steps = int(sharding.sum_over_ranks(float(live_steps), device=None if shared else dev)) * 15
     value = veh_steps / elapsed
-    rd, wr = state_bytes(args.dtype)
-    # per env.step launch: the state, the step tail and (Kinematics) the observation (launch_bytes)
-    # config 3: the launch writes the OccupancyGrid too (ttrl_env_step_grid) unless the A/B switch
-    # TTRL_FUSE_GRID=0 left it to the grid kernel (roofline_obs)
-    fused_grid = C["obs"]["type"] == "OccupancyGrid" and not grid_launches
-    cells = int(np.prod(env.observation_space.shape)) if fused_grid else 0
-    alg_bytes = launch_bytes(E, N, args.dtype, C["obs"], graph=ix, grid_cells=cells,
-                             ix_tail=ix and getattr(env, "_fuse", False))
-    kernel = "simulate_kernel (fused 15-frame Road.act+Road.step + step tail)"
-    if C["obs"]["type"] == "Kinematics":  # the launch also writes the observation (ttrl_env_step)
-        kernel = "simulate_kernel (fused 15-frame Road.act+Road.step + Kinematics observation + step tail)"
-    if fused_grid:
-        kernel = "simulate_grid_kernel (fused 15-frame Road.act+Road.step + OccupancyGrid + step tail)"
-    if ix and getattr(env, "_fuse", False):  # ttrl_ix_env_step: + _clear_vehicles / _spawn_vehicle, the swap
-        kernel = ("simulate_ix_kernel (fused 15-frame Road.act+Road.step + Kinematics observation + step tail "
-                  "+ _clear_vehicles / _spawn_vehicle + the finished envs' spare scenes)")
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    pmc, pmc_source = read_pmc(args.dtype, args.config)
-    hbm = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-           "traffic": (pmc or {}).get("hbm_bytes_per_launch"), "traffic_source": pmc_source}
     out = {
         "metric": "vehicle-steps/sec at 4096 envs×64 vehicles; 1/2/4/8 GPUs; HBM GB/s achieved",
         "value": value,
@@ -552,46 +609,69 @@ def main():
                    "frames_per_step": 15,
                    "observation": C["obs"]["type"], "parallelism": f"env-sharded x{world}, no collective on the step",
                    "hip_graph": bool(args.graph), "auto_reset": bool(args.auto_reset or ix)},
-        # the HBM roofline of the fused launch: algorithmic bytes (state read + written once, the
-        # observation written once) over the launch time measured here with HIP events
-        "roofline": dict(bound="hbm", **hbm, kernel=kernel, kernel_ms=kern_ms, alg_bytes_per_launch=alg_bytes,
-                         alg_bytes_per_vehicle_step=alg_bytes / (E * N * 15.0)),
         "env_steps_per_s": global_envs * args.steps / elapsed,
     }
-    if pmc and pmc.get("valu_active_cycles_per_wave") and pmc.get("sq_waves"):
-        # The roofline that binds: the fused kernel is VALU-issue / latency bound,
-        # not HBM bound.  From the PMC profile of this build of the kernel (hash-checked):
-        # SQ_ACTIVE_INST_VALU (quad-cycles, x4) over the launch's waves against every SIMD's cycles in
-        # the kernel time measured here (1024 SIMDs x the GRBM clock) -- the VALU-busy fraction.
-        # The bound is the larger of the two fractions; the HBM view stays in roofline["hbm"].
-        waves = pmc["sq_waves"]
-        clk = pmc.get("effective_clock_ghz") or 2.4
-        simd_cycles_per_s = 1024 * clk * 1e9
-        active = pmc["valu_active_cycles_per_wave"] * waves
-        busy = active / (simd_cycles_per_s * kern_ms * 1e-3)
-        if busy > hbm["frac"]:
-            out["roofline"] = dict(bound="valu", achieved=active / (kern_ms * 1e-3), peak=simd_cycles_per_s,
-                                   unit="VALU-busy SIMD cycles/s", frac=busy, traffic=hbm["traffic"],
-                                   kernel=kernel, kernel_ms=kern_ms, alg_bytes_per_launch=alg_bytes,
-                                   alg_bytes_per_vehicle_step=alg_bytes / (E * N * 15.0), hbm=hbm,
-                                   valu_insts_per_launch=pmc["valu_insts_per_wave"] * waves,
-                                   counters=pmc_source + ": SQ_ACTIVE_INST_VALU, SQ_INSTS_VALU, SQ_WAVES, "
-                                                         "GRBM_GUI_ACTIVE")
-    if grid_launches and C["obs"]["type"] == "OccupancyGrid":
-        # the grid kernel: algorithmic bytes = each vehicle's x, y, heading, speed, lane, kind read
-        # once + the [E, F, W, H] float32 grid written once
-        g_ms = float(np.mean([s_.elapsed_time(e_) for s_, e_ in grid_launches]))
-        r_ = 8 if args.dtype == "f64" else 4
-        cells = len(C["obs"]["features"]) * int(np.prod(env.observation_space.shape[1:]))
-        g_bytes = E * (N * (4 * r_ + 4 + 1) + cells * 4)
-        g_ach = g_bytes / (g_ms * 1e-3) / 1e9
-        out["roofline_obs"] = {"bound": "hbm", "achieved": g_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                               "frac": g_ach / HBM_PEAK_GBS, "traffic": (pmc or {}).get("grid_hbm_bytes_per_launch"),
-                               "kernel": "grid_obs_kernel (OccupancyGridObservation.observe)", "kernel_ms": g_ms,
-                               "alg_bytes_per_launch": g_bytes}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full:
+        kern_ms = float(np.mean(kern_warm)) if sg is not None else float(np.mean([span(r) for r in launches if r]))
+        # per env.step launch: the state, the step tail and (Kinematics) the observation (launch_bytes)
+        # config 3: the launch writes the OccupancyGrid too (ttrl_env_step_grid) unless the A/B switch
+        # TTRL_FUSE_GRID=0 left it to the grid kernel (roofline_obs)
+        fused_grid = C["obs"]["type"] == "OccupancyGrid" and not grid_launches
+        cells = int(np.prod(env.observation_space.shape)) if fused_grid else 0
+        alg_bytes = launch_bytes(E, N, args.dtype, C["obs"], graph=ix, grid_cells=cells,
+                                 ix_tail=ix and getattr(env, "_fuse", False))
+        kernel = "simulate_kernel (fused 15-frame Road.act+Road.step + step tail)"
+        if C["obs"]["type"] == "Kinematics":  # the launch also writes the observation (ttrl_env_step)
+            kernel = "simulate_kernel (fused 15-frame Road.act+Road.step + Kinematics observation + step tail)"
+        if fused_grid:
+            kernel = "simulate_grid_kernel (fused 15-frame Road.act+Road.step + OccupancyGrid + step tail)"
+        if ix and getattr(env, "_fuse", False):  # ttrl_ix_env_step: + _clear_vehicles / _spawn_vehicle, the swap
+            kernel = ("simulate_ix_kernel (fused 15-frame Road.act+Road.step + Kinematics observation + step tail "
+                      "+ _clear_vehicles / _spawn_vehicle + the finished envs' spare scenes)")
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+        pmc, pmc_source = read_pmc(args.dtype, args.config)
+        hbm = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+               "traffic": (pmc or {}).get("hbm_bytes_per_launch"), "traffic_source": pmc_source}
+        # the HBM roofline of the fused launch: algorithmic bytes (state read + written once, the
+        # observation written once) over the launch time measured here with HIP events
+        out["roofline"] = dict(bound="hbm", **hbm, kernel=kernel, kernel_ms=kern_ms, alg_bytes_per_launch=alg_bytes,
+                               alg_bytes_per_vehicle_step=alg_bytes / (E * N * 15.0))
+        if pmc and pmc.get("valu_active_cycles_per_wave") and pmc.get("sq_waves"):
+            # The roofline that binds: the fused kernel is VALU-issue / latency bound,
+            # not HBM bound.  From the PMC profile of this build of the kernel (hash-checked):
+            # SQ_ACTIVE_INST_VALU (quad-cycles, x4) over the launch's waves against every SIMD's cycles in
+            # the kernel time measured here (1024 SIMDs x the GRBM clock) -- the VALU-busy fraction.
+            # The bound is the larger of the two fractions; the HBM view stays in roofline["hbm"].
+            waves = pmc["sq_waves"]
+            clk = pmc.get("effective_clock_ghz") or 2.4
+            simd_cycles_per_s = 1024 * clk * 1e9
+            active = pmc["valu_active_cycles_per_wave"] * waves
+            busy = active / (simd_cycles_per_s * kern_ms * 1e-3)
+            if busy > hbm["frac"]:
+                out["roofline"] = dict(bound="valu", achieved=active / (kern_ms * 1e-3), peak=simd_cycles_per_s,
+                                       unit="VALU-busy SIMD cycles/s", frac=busy, traffic=hbm["traffic"],
+                                       kernel=kernel, kernel_ms=kern_ms, alg_bytes_per_launch=alg_bytes,
+                                       alg_bytes_per_vehicle_step=alg_bytes / (E * N * 15.0), hbm=hbm,
+                                       valu_insts_per_launch=pmc["valu_insts_per_wave"] * waves,
+                                       counters=pmc_source + ": SQ_ACTIVE_INST_VALU, SQ_INSTS_VALU, SQ_WAVES, "
+                                                             "GRBM_GUI_ACTIVE")
+        if grid_launches and C["obs"]["type"] == "OccupancyGrid":
+            # the grid kernel: algorithmic bytes = each vehicle's x, y, heading, speed, lane, kind read
+            # once + the [E, F, W, H] float32 grid written once
+            g_ms = float(np.mean([s_.elapsed_time(e_) for s_, e_ in grid_launches]))
+            r_ = 8 if args.dtype == "f64" else 4
+            cells = len(C["obs"]["features"]) * int(np.prod(env.observation_space.shape[1:]))
+            g_bytes = E * (N * (4 * r_ + 4 + 1) + cells * 4)
+            g_ach = g_bytes / (g_ms * 1e-3) / 1e9
+            out["roofline_obs"] = {"bound": "hbm", "achieved": g_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                   "frac": g_ach / HBM_PEAK_GBS, "traffic": (pmc or {}).get("grid_hbm_bytes_per_launch"),
+                                   "kernel": "grid_obs_kernel (OccupancyGridObservation.observe)", "kernel_ms": g_ms,
+                                   "alg_bytes_per_launch": g_bytes}
     if ix:
         out["config"]["live_vehicles_per_env"] = veh_steps / (global_envs * 15 * args.steps)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = (cpu_baseline_ix(args.cpu_seconds) if ix else
                                cpu_baseline(N, C["obs"] if C["obs"]["type"] == "Kinematics" else GRID7,
                                             args.cpu_seconds, envs=E, threads=1 if E == 1 else None))
