@@ -5233,23 +5233,11 @@ __global__ void __launch_bounds__(64) copy_envs_kernel(ttrl_state_t dst, ttrl_st
 // A network beyond one road, or a RegulatedRoad: the simulate kernel's NET_GRAPH instance.
 bool is_graph(const ttrl_lane_table_t& R) { return R.n_roads > 1 || R.regulation_frequency > 0; }
 
-// TTRL_OK, a negative TTRL_E_* code, or EMPTY (> 0: no env, nothing to do -- the entry points
-// then return TTRL_OK before looking at buffers an empty batch need not have)
 #ifndef TTRL_KERNEL_ONLY  // host launchers
-constexpr int EMPTY = 1;
-int check_state(const ttrl_state_t* s, const ttrl_lane_table_t* R) {
-  if (!s || !R) return TTRL_E_ARG;
-  if (s->dtype != TTRL_F32 && s->dtype != TTRL_F64) return TTRL_E_ARG;
-  if (s->n_envs < 0 || s->n_veh < 1 || s->n_veh > 256) return TTRL_E_ARG;
-  if (s->n_envs == 0) return EMPTY;
-  if (R->n_lanes < 1 || R->n_lanes > LMAX) return TTRL_E_ARG;
-  if (R->n_roads < 1 || R->n_roads > TTRL_MAX_ROADS || R->regulation_frequency < 0) return TTRL_E_ARG;
-  for (int l = 0; l < R->n_lanes; ++l)  // topology consistent (lanes of a road contiguous, in id order)
-    if (R->road[l] < 0 || R->road[l] >= R->n_roads || R->road_first[R->road[l]] + R->lane_id[l] != l ||
-        R->lane_id[l] >= R->road_n[R->road[l]])
-      return TTRL_E_ARG;
-  if (is_graph(*R) && (!s->route_road || !s->route_lane || !s->route_n || !s->yielding || !s->reg_steps))
-    return TTRL_E_ARG;
+// ---- argument checks: TTRL_OK or a negative TTRL_E_* code, each fact of the ABI written once
+
+// The 18 rows every state needs (the route, regulation and rng rows depend on the road and the entry).
+int check_rows(const ttrl_state_t* s) {
   const void* ptrs[] = {s->x, s->y, s->heading, s->speed, s->target_speed, s->timer, s->delta, s->steer, s->acc,
                         s->impact_x, s->impact_y, s->lane, s->target_lane, s->speed_index, s->kind, s->crashed,
                         s->has_impact, s->lane_change};
@@ -5258,25 +5246,145 @@ int check_state(const ttrl_state_t* s, const ttrl_lane_table_t* R) {
   return TTRL_OK;
 }
 
+// The route and regulation rows a road network needs.
+bool has_net_rows(const ttrl_state_t* s) {
+  return s->route_road && s->route_lane && s->route_n && s->yielding && s->reg_steps;
+}
+
+bool shape_ok(const ttrl_state_t* s) {
+  return (s->dtype == TTRL_F32 || s->dtype == TTRL_F64) && s->n_envs >= 0 && s->n_veh >= 1 && s->n_veh <= 256;
+}
+
+// TTRL_OK, a negative TTRL_E_* code, or EMPTY (> 0: no env, nothing to do -- the entry points
+// then return TTRL_OK before looking at buffers an empty batch need not have)
+constexpr int EMPTY = 1;
+int check_state(const ttrl_state_t* s, const ttrl_lane_table_t* R) {
+  if (!s || !R || !shape_ok(s)) return TTRL_E_ARG;
+  if (s->n_envs == 0) return EMPTY;
+  if (R->n_lanes < 1 || R->n_lanes > LMAX) return TTRL_E_ARG;
+  if (R->n_roads < 1 || R->n_roads > TTRL_MAX_ROADS || R->regulation_frequency < 0) return TTRL_E_ARG;
+  for (int l = 0; l < R->n_lanes; ++l)  // topology consistent (lanes of a road contiguous, in id order)
+    if (R->road[l] < 0 || R->road[l] >= R->n_roads || R->road_first[R->road[l]] + R->lane_id[l] != l ||
+        R->lane_id[l] >= R->road_n[R->road[l]])
+      return TTRL_E_ARG;
+  if (is_graph(*R) && !has_net_rows(s)) return TTRL_E_ARG;
+  return check_rows(s);
+}
+
+int check_params(const ttrl_params_t* P) {
+  return P && P->n_target_speeds >= 1 && P->n_target_speeds <= 8 ? TTRL_OK : TTRL_E_ARG;
+}
+
+int check_reset_cfg(const ttrl_state_t* s, const ttrl_lane_table_t* R, const ttrl_reset_cfg_t* cfg) {
+  return cfg && cfg->n_vehicles >= 1 && cfg->n_vehicles <= s->n_veh && cfg->ego_lane >= 0 && cfg->ego_lane < R->n_lanes
+             ? TTRL_OK : TTRL_E_ARG;
+}
+
+int check_grid_cfg(const ttrl_grid_cfg_t* cfg, const float* out) {
+  if (!cfg || !out || cfg->n_features < 1 || cfg->n_features > TTRL_N_FEATURES || cfg->shape_x < 1 ||
+      cfg->shape_y < 1 || cfg->step_x <= 0 || cfg->step_y <= 0)
+    return TTRL_E_ARG;
+  for (int c = 0; c < cfg->n_features; ++c)
+    if (cfg->features[c] < 0 || cfg->features[c] >= TTRL_N_FEATURES) return TTRL_E_ARG;
+  return TTRL_OK;
+}
+
+int check_kin_cfg(const ttrl_state_t* s, const ttrl_kin_cfg_t* cfg) {
+  if (!cfg || cfg->vehicles_count < 1 || cfg->n_features < 1 || cfg->n_features > TTRL_N_FEATURES) return TTRL_E_ARG;
+  if (cfg->order_shuffled < 0 || cfg->order_shuffled > 2) return TTRL_E_ARG;
+  if (cfg->order_shuffled == 2 && (!s->rng || cfg->vehicles_count - 1 > 64)) return TTRL_E_ARG;
+  for (int c = 0; c < cfg->n_features; ++c)
+    if (cfg->features[c] < 0 || cfg->features[c] >= TTRL_F_ON_ROAD) return TTRL_E_ARG;
+  return TTRL_OK;
+}
+
+// The step tail's outputs (ttrl_rewards_step): all four, and the info's ego speed / crashed both or neither.
+bool reward_out_ok(const double* time, const float* reward, const uint8_t* terminated, const uint8_t* truncated,
+                   const void* ego_speed, const uint8_t* ego_crashed) {
+  return time && reward && terminated && truncated && (!ego_speed) == (!ego_crashed);
+}
+
 int slots_for(int n) { return n <= 32 ? 32 : n <= 64 ? 64 : n <= 128 ? 128 : 256; }
 
-// The reset instance for a road: CV = false when every lane is straight along +x (the highway).
+// What a step entry point adds after the last frame, checked and put into `so`: the Kinematics
+// observation (need_obs: the entry requires it, else a null obs_cfg with a null obs skips it), the
+// step tail (need_reward likewise; null reward_cfg: skipped) and the action LUT.  max_slots: the
+// largest slot class the entry's launch takes; beyond it TTRL_E_UNSUPPORTED, reported where
+// ttrl_ix_env_step always has: after the null and range checks, ahead of the LUT's codes.
+int fill_step_out(StepOut& so, const ttrl_state_t* s, bool need_obs, const ttrl_kin_cfg_t* obs_cfg, float* obs,
+                  int32_t* obs_ids, bool need_reward, const ttrl_reward_cfg_t* reward_cfg, double* time,
+                  double time_inc, float* reward, uint8_t* terminated, uint8_t* truncated, float* components,
+                  void* ego_speed, uint8_t* ego_crashed, const int32_t* action_lut, int32_t n_action_lut,
+                  int max_slots = 256) {
+  if ((need_obs && !obs_cfg) || (!obs_cfg) != (!obs) || (obs_cfg && check_kin_cfg(s, obs_cfg))) return TTRL_E_ARG;
+  if (need_reward && !reward_cfg) return TTRL_E_ARG;
+  if (reward_cfg && !reward_out_ok(time, reward, terminated, truncated, ego_speed, ego_crashed)) return TTRL_E_ARG;
+  if (n_action_lut < 0 || n_action_lut > 8 || (n_action_lut > 0 && !action_lut)) return TTRL_E_ARG;
+  if (slots_for(s->n_veh) > max_slots) return TTRL_E_UNSUPPORTED;
+  for (int q = 0; q < n_action_lut; ++q) {
+    if (action_lut[q] < TTRL_LANE_LEFT || action_lut[q] > TTRL_SLOWER) return TTRL_E_ARG;
+    so.lut[q] = (int8_t)action_lut[q];
+  }
+  so.n_lut = n_action_lut;
+  if (obs_cfg) { so.kcfg = *obs_cfg; so.obs = obs; so.ids = obs_ids; }
+  if (reward_cfg) {
+    so.rcfg = *reward_cfg; so.time = time; so.time_inc = time_inc; so.reward = reward; so.term = terminated;
+    so.trunc = truncated; so.comp = components; so.ego_speed = ego_speed; so.ego_crashed = ego_crashed;
+  }
+  return TTRL_OK;
+}
+
+// ---- dispatch on the state's dtype and slot class
+
+int launch_status() { return hipGetLastError() == hipSuccess ? TTRL_OK : TTRL_E_LAUNCH; }
+
+// f(T{}) with T the state's real type: `with_real(s->dtype, [&](auto real) { using T = decltype(real); ... })`
+template <typename F>
+auto with_real(int dtype, F f) {
+  if (dtype == TTRL_F64) return f(double{});
+  return f(float{});
+}
+// ... for an f that only launches: the launch's status
+template <typename F>
+int launch_real(int dtype, F f) {
+  with_real(dtype, f);
+  return launch_status();
+}
+
+// f(Slots<NS, EPW>{}) with the workgroup of the per-slot kernels (simulate, neighbours, kinematics)
+// for n_veh vehicles per env: NS slots per env, two envs sharing a wave64 on 32 slots
+template <int NS_, int EPW_> struct Slots { static constexpr int NS = NS_, EPW = EPW_; };
+template <typename F>
+int with_slots(int n_veh, F f) {
+  switch (slots_for(n_veh)) {
+    case 32: return f(Slots<32, 2>{});
+    case 64: return f(Slots<64, 1>{});
+    case 128: return f(Slots<128, 1>{});
+    default: return f(Slots<256, 1>{});
+  }
+}
+
+// ---- launchers
+
+// Every lane is straight along +x (the highway).
+bool straight_along_x(const ttrl_lane_table_t& R) {
+  for (int l = 0; l < R.n_lanes; ++l)
+    if (R.type[l] != TTRL_LANE_STRAIGHT || R.dir_x[l] != 1.0 || R.dir_y[l] != 0.0) return false;
+  return true;
+}
+
+// The reset instance for a road: CV = false when every lane is straight along +x.
 template <typename T>
 void launch_reset(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P,
                   const ttrl_reset_cfg_t& cfg, const unsigned long long* pcg, unsigned* words, int n_words,
                   const uint8_t* mask, const AutoReset& ar, hipStream_t st) {
-  bool curved = false;
-  for (int l = 0; l < R.n_lanes; ++l)
-    curved |= R.type[l] != TTRL_LANE_STRAIGHT || R.dir_x[l] != 1.0 || R.dir_y[l] != 0.0;
-  if (curved)
+  if (!straight_along_x(R))
     hipLaunchKernelGGL((reset_wave_kernel<T, true>), dim3(s.n_envs), dim3(64), 0, st, s, R, P, cfg, pcg, words,
                        n_words, mask, ar);
   else
     hipLaunchKernelGGL((reset_wave_kernel<T, false>), dim3(s.n_envs), dim3(64), 0, st, s, R, P, cfg, pcg, words,
                        n_words, mask, ar);
 }
-
-int launch_status() { return hipGetLastError() == hipSuccess ? TTRL_OK : TTRL_E_LAUNCH; }
 
 // ttrl_env_step's tail scratch (the observation's keys, rows and counts; simulate_body's epilogue)
 // fits the act phase's block it overlays (dead after the last frame).
@@ -5317,48 +5425,25 @@ int launch_sim(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_par
   const bool graph = is_graph(R);
   // the NET_STRAIGHT instance: at most STRAIGHT_LANE_CAP straight lanes along +x; any other road
   // (curved, rotated or wider) runs the NET_CURVED instance, which handles every lane class
-  bool curved = R.n_lanes > STRAIGHT_LANE_CAP;
-  for (int l = 0; l < R.n_lanes; ++l)
-    curved |= R.type[l] != TTRL_LANE_STRAIGHT || R.dir_x[l] != 1.0 || R.dir_y[l] != 0.0;
-  const size_t lds = host_view_bytes(sizeof(T) == 8 ? TTRL_F64 : TTRL_F32, EPW, NS,
-                                     graph || curved ? R.n_lanes : STRAIGHT_LANE_CAP, graph,
-                                     !graph && !curved && sorted_view(NS, EPW, NET_STRAIGHT));
-  if (ob.obs || ob.reward) {  // the tail's scratch must fit the dead block it overlays (it does for every NS)
-    const ViewLayout o = view_layout<T>(EPW, NS, graph || curved ? R.n_lanes : STRAIGHT_LANE_CAP, graph,
-                                        !graph && !curved && sorted_view(NS, EPW, NET_STRAIGHT));
-    if (!tail_fits<T>(o, EPW, NS)) return TTRL_E_UNSUPPORTED;
-  }
+  const bool curved = R.n_lanes > STRAIGHT_LANE_CAP || !straight_along_x(R);
+  const ViewLayout o = view_layout<T>(EPW, NS, graph || curved ? R.n_lanes : STRAIGHT_LANE_CAP, graph,
+                                      !graph && !curved && sorted_view(NS, EPW, NET_STRAIGHT));
+  // the tail's scratch must fit the dead block it overlays (it does for every NS)
+  if ((ob.obs || ob.reward) && !tail_fits<T>(o, EPW, NS)) return TTRL_E_UNSUPPORTED;
   const ParamsT<T> PT = params_for<T>(P);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(NS * EPW), o.total, stream, s, R, PT, actions, mask, frames, dt, mode,
+                       ablate, ob);
+    return launch_status();
+  };
   if constexpr (NS == 32 && EPW == 2) {
     // every wave resident at 2 per SIMD: the 2-wave register budget (no spills) costs no occupancy
-    if (!graph && !curved && blocks <= 2 * simds_of_stream_device(stream)) {
-      hipLaunchKernelGGL((simulate_kernel<T, NS, EPW, NET_STRAIGHT, 2>), dim3(blocks), dim3(NS * EPW), lds, stream,
-                         s, R, PT, actions, mask, frames, dt, mode, ablate, ob);
-      return launch_status();
-    }
+    if (!graph && !curved && blocks <= 2 * simds_of_stream_device(stream))
+      return launch(simulate_kernel<T, NS, EPW, NET_STRAIGHT, 2>);
   }
-  if (graph)
-    hipLaunchKernelGGL((simulate_kernel<T, NS, EPW, NET_GRAPH>), dim3(blocks), dim3(NS * EPW), lds, stream, s, R, PT,
-                       actions, mask, frames, dt, mode, ablate, ob);
-  else if (curved)
-    hipLaunchKernelGGL((simulate_kernel<T, NS, EPW, NET_CURVED>), dim3(blocks), dim3(NS * EPW), lds, stream, s, R,
-                       PT, actions, mask, frames, dt, mode, ablate, ob);
-  else
-    hipLaunchKernelGGL((simulate_kernel<T, NS, EPW, NET_STRAIGHT>), dim3(blocks), dim3(NS * EPW), lds, stream, s, R,
-                       PT, actions, mask, frames, dt, mode, ablate, ob);
-  return launch_status();
-}
-
-template <typename T>
-int dispatch_sim(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P, const int32_t* actions,
-                 const uint8_t* mask, int frames, double dt, int mode, int ablate, hipStream_t stream,
-                 const StepOut& ob) {
-  switch (slots_for(s.n_veh)) {
-    case 32: return launch_sim<T, 32, 2>(s, R, P, actions, mask, frames, dt, mode, ablate, stream, ob);
-    case 64: return launch_sim<T, 64, 1>(s, R, P, actions, mask, frames, dt, mode, ablate, stream, ob);
-    case 128: return launch_sim<T, 128, 1>(s, R, P, actions, mask, frames, dt, mode, ablate, stream, ob);
-    default: return launch_sim<T, 256, 1>(s, R, P, actions, mask, frames, dt, mode, ablate, stream, ob);
-  }
+  if (graph) return launch(simulate_kernel<T, NS, EPW, NET_GRAPH>);
+  if (curved) return launch(simulate_kernel<T, NS, EPW, NET_CURVED>);
+  return launch(simulate_kernel<T, NS, EPW, NET_STRAIGHT>);
 }
 
 // ttrl_ix_env_step's launch: the one-wavefront road-network instance with the fused tail (IxEpi)
@@ -5397,9 +5482,7 @@ int launch_sim_grid(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttr
 // The road and slot count run the straight one-env-per-workgroup instance with a sorted view
 // (launch_sim's choice for 64 and 128 slots on <= STRAIGHT_LANE_CAP straight lanes along +x).
 bool grid_fusable(const ttrl_state_t& s, const ttrl_lane_table_t& R) {
-  if (is_graph(R) || R.n_lanes > STRAIGHT_LANE_CAP) return false;
-  for (int l = 0; l < R.n_lanes; ++l)
-    if (R.type[l] != TTRL_LANE_STRAIGHT || R.dir_x[l] != 1.0 || R.dir_y[l] != 0.0) return false;
+  if (is_graph(R) || R.n_lanes > STRAIGHT_LANE_CAP || !straight_along_x(R)) return false;
   const int ns = slots_for(s.n_veh);
   return ns == 64 || ns == 128;
 }
@@ -5409,72 +5492,16 @@ int run_sim(const ttrl_state_t* s, const ttrl_lane_table_t* R, const ttrl_params
             const StepOut* ob = nullptr) {
   int rc = check_state(s, R);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!P || frames < 0 || P->n_target_speeds < 1 || P->n_target_speeds > 8) return TTRL_E_ARG;
+  if (frames < 0 || check_params(P)) return TTRL_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const StepOut none{};
   const StepOut& o = ob ? *ob : none;
-  return s->dtype == TTRL_F64 ? dispatch_sim<double>(*s, *R, *P, actions, mask, frames, dt, mode, ablate, st, o)
-                              : dispatch_sim<float>(*s, *R, *P, actions, mask, frames, dt, mode, ablate, st, o);
-}
-
-int check_grid_cfg(const ttrl_grid_cfg_t* cfg, const float* out) {
-  if (!cfg || !out || cfg->n_features < 1 || cfg->n_features > TTRL_N_FEATURES || cfg->shape_x < 1 ||
-      cfg->shape_y < 1 || cfg->step_x <= 0 || cfg->step_y <= 0)
-    return TTRL_E_ARG;
-  for (int c = 0; c < cfg->n_features; ++c)
-    if (cfg->features[c] < 0 || cfg->features[c] >= TTRL_N_FEATURES) return TTRL_E_ARG;
-  return TTRL_OK;
-}
-
-int check_kin_cfg(const ttrl_state_t* s, const ttrl_kin_cfg_t* cfg) {
-  if (!cfg || cfg->vehicles_count < 1 || cfg->n_features < 1 || cfg->n_features > TTRL_N_FEATURES) return TTRL_E_ARG;
-  if (cfg->order_shuffled < 0 || cfg->order_shuffled > 2) return TTRL_E_ARG;
-  if (cfg->order_shuffled == 2 && (!s->rng || cfg->vehicles_count - 1 > 64)) return TTRL_E_ARG;
-  for (int c = 0; c < cfg->n_features; ++c)
-    if (cfg->features[c] < 0 || cfg->features[c] >= TTRL_F_ON_ROAD) return TTRL_E_ARG;
-  return TTRL_OK;
-}
-
-template <typename T, int NS, int EPW>
-int launch_nbr(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P, const int32_t* q,
-               int32_t* f, int32_t* r, hipStream_t stream) {
-  const int blocks = (s.n_envs + EPW - 1) / EPW;
-  if (blocks == 0) return TTRL_OK;
-  const size_t lds = host_view_bytes(sizeof(T) == 8 ? TTRL_F64 : TTRL_F32, EPW, NS, R.n_lanes);
-  hipLaunchKernelGGL((neighbours_kernel<T, NS, EPW>), dim3(blocks), dim3(NS * EPW), lds, stream, s, R, P, q, f, r);
-  return launch_status();
-}
-
-template <typename T>
-int dispatch_nbr(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P, const int32_t* q,
-                 int32_t* f, int32_t* r, hipStream_t st) {
-  switch (slots_for(s.n_veh)) {
-    case 32: return launch_nbr<T, 32, 2>(s, R, P, q, f, r, st);
-    case 64: return launch_nbr<T, 64, 1>(s, R, P, q, f, r, st);
-    case 128: return launch_nbr<T, 128, 1>(s, R, P, q, f, r, st);
-    default: return launch_nbr<T, 256, 1>(s, R, P, q, f, r, st);
-  }
-}
-
-template <typename T, int NS, int EPW>
-int launch_kin(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P, const ttrl_kin_cfg_t& c,
-               const uint8_t* mask, float* out, int32_t* ids, hipStream_t stream) {
-  const int blocks = (s.n_envs + EPW - 1) / EPW;
-  if (blocks == 0) return TTRL_OK;
-  hipLaunchKernelGGL((kinematics_obs_kernel<T, NS, EPW>), dim3(blocks), dim3(NS * EPW), 0, stream, s, R, P, c, mask,
-                     out, ids);
-  return launch_status();
-}
-
-template <typename T>
-int dispatch_kin(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P, const ttrl_kin_cfg_t& c,
-                 const uint8_t* mask, float* out, int32_t* ids, hipStream_t st) {
-  switch (slots_for(s.n_veh)) {
-    case 32: return launch_kin<T, 32, 2>(s, R, P, c, mask, out, ids, st);
-    case 64: return launch_kin<T, 64, 1>(s, R, P, c, mask, out, ids, st);
-    case 128: return launch_kin<T, 128, 1>(s, R, P, c, mask, out, ids, st);
-    default: return launch_kin<T, 256, 1>(s, R, P, c, mask, out, ids, st);
-  }
+  return with_real(s->dtype, [&](auto real) {
+    return with_slots(s->n_veh, [&](auto w) {
+      using W = decltype(w);
+      return launch_sim<decltype(real), W::NS, W::EPW>(*s, *R, *P, actions, mask, frames, dt, mode, ablate, st, o);
+    });
+  });
 }
 
 #endif  // TTRL_KERNEL_ONLY
@@ -5487,6 +5514,9 @@ void* const kernel_only_refs[] = {(void*)&simulate_kernel<double, 64, 1, NET_STR
 #ifndef TTRL_KERNEL_ONLY
 
 // ===================================================================== C ABI
+// An entry point that takes a state and its road runs check_state first (an empty batch returns
+// TTRL_OK before any other argument is looked at), then checks its own arguments, then launches
+// on the state's dtype (with_real).
 extern "C" {
 
 int ttrl_abi_version(void) { return TTRL_ABI_VERSION; }
@@ -5525,30 +5555,21 @@ int ttrl_env_step_grid(const ttrl_state_t* s, const ttrl_lane_table_t* road, con
                        stream);
     return rc ? rc : ttrl_observe_grid(s, road, p, grid_cfg, grid, stream);
   }
-  if (!p || frames < 0 || p->n_target_speeds < 1 || p->n_target_speeds > 8) return TTRL_E_ARG;
-  if (reward_cfg && (!time || !reward || !terminated || !truncated || (!ego_speed) != (!ego_crashed)))
-    return TTRL_E_ARG;
-  if (n_action_lut < 0 || n_action_lut > 8 || (n_action_lut > 0 && !action_lut)) return TTRL_E_ARG;
+  if (frames < 0 || check_params(p)) return TTRL_E_ARG;
   StepOut so{};
-  for (int q = 0; q < n_action_lut; ++q) {
-    if (action_lut[q] < TTRL_LANE_LEFT || action_lut[q] > TTRL_SLOWER) return TTRL_E_ARG;
-    so.lut[q] = (int8_t)action_lut[q];
-  }
-  so.n_lut = n_action_lut;
-  if (reward_cfg) {
-    so.rcfg = *reward_cfg; so.time = time; so.time_inc = time_inc; so.reward = reward; so.term = terminated;
-    so.trunc = truncated; so.comp = components; so.ego_speed = ego_speed; so.ego_crashed = ego_crashed;
-  }
+  if ((rc = fill_step_out(so, s, false, nullptr, nullptr, nullptr, false, reward_cfg, time, time_inc, reward,
+                          terminated, truncated, components, ego_speed, ego_crashed, action_lut, n_action_lut)))
+    return rc;
   GridEpi ge{};
   ge.cfg = *grid_cfg;
   ge.out = grid;
   hipStream_t st = (hipStream_t)stream;
   const bool wide = slots_for(s->n_veh) == 128;
-  if (s->dtype == TTRL_F64)
-    return wide ? launch_sim_grid<double, 128>(*s, *road, *p, actions, frames, dt, st, so, ge)
-                : launch_sim_grid<double, 64>(*s, *road, *p, actions, frames, dt, st, so, ge);
-  return wide ? launch_sim_grid<float, 128>(*s, *road, *p, actions, frames, dt, st, so, ge)
-              : launch_sim_grid<float, 64>(*s, *road, *p, actions, frames, dt, st, so, ge);
+  return with_real(s->dtype, [&](auto real) {
+    using T = decltype(real);
+    return wide ? launch_sim_grid<T, 128>(*s, *road, *p, actions, frames, dt, st, so, ge)
+                : launch_sim_grid<T, 64>(*s, *road, *p, actions, frames, dt, st, so, ge);
+  });
 }
 
 int ttrl_env_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p, const int32_t* actions,
@@ -5558,21 +5579,10 @@ int ttrl_env_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, const tt
                   const int32_t* order, const int32_t* action_lut, int32_t n_action_lut, void* stream) {
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if ((!obs_cfg) != (!obs) || (obs_cfg && check_kin_cfg(s, obs_cfg))) return TTRL_E_ARG;
-  if (reward_cfg && (!time || !reward || !terminated || !truncated || (!ego_speed) != (!ego_crashed)))
-    return TTRL_E_ARG;
-  if (n_action_lut < 0 || n_action_lut > 8 || (n_action_lut > 0 && !action_lut)) return TTRL_E_ARG;
   StepOut so{};
-  for (int q = 0; q < n_action_lut; ++q) {
-    if (action_lut[q] < TTRL_LANE_LEFT || action_lut[q] > TTRL_SLOWER) return TTRL_E_ARG;
-    so.lut[q] = (int8_t)action_lut[q];
-  }
-  so.n_lut = n_action_lut;
-  if (obs_cfg) { so.kcfg = *obs_cfg; so.obs = obs; so.ids = obs_ids; }
-  if (reward_cfg) {
-    so.rcfg = *reward_cfg; so.time = time; so.time_inc = time_inc; so.reward = reward; so.term = terminated;
-    so.trunc = truncated; so.comp = components; so.ego_speed = ego_speed; so.ego_crashed = ego_crashed;
-  }
+  if ((rc = fill_step_out(so, s, false, obs_cfg, obs, obs_ids, false, reward_cfg, time, time_inc, reward, terminated,
+                          truncated, components, ego_speed, ego_crashed, action_lut, n_action_lut)))
+    return rc;
   so.order = order;
   return run_sim(s, road, p, actions, frames, dt, MODE_META | MODE_ACT | MODE_STEP, stream, 0, nullptr, &so);
 }
@@ -5585,8 +5595,9 @@ long ttrl_diag_view_bytes(int32_t dtype, int32_t epw, int32_t ns, int32_t n_lane
 /* Diagnostic only (not in include/): the flattened enforcement's queue capacity of a road-network
  * view (0: the serial pair loop runs). */
 long ttrl_diag_rq_cap(int32_t dtype, int32_t epw, int32_t ns, int32_t n_lanes) {
-  return (long)(dtype == TTRL_F64 ? view_layout<double>(epw, ns, n_lanes, true, false).rq_cap
-                                  : view_layout<float>(epw, ns, n_lanes, true, false).rq_cap);
+  return with_real(dtype, [&](auto real) {
+    return (long)view_layout<decltype(real)>(epw, ns, n_lanes, true, false).rq_cap;
+  });
 }
 
 /* Diagnostic only (not in include/): the fused loop with phases ablated, for profiling. */
@@ -5628,8 +5639,15 @@ int ttrl_neighbours(const ttrl_state_t* s, const ttrl_lane_table_t* road, const 
   ttrl_params_t P{};
   P.lane_vehicle_length = 5.0;  // AbstractLane.VEHICLE_LENGTH
   hipStream_t st = (hipStream_t)stream;
-  return s->dtype == TTRL_F64 ? dispatch_nbr<double>(*s, *road, P, query_lane, front, rear, st)
-                              : dispatch_nbr<float>(*s, *road, P, query_lane, front, rear, st);
+  return with_real(s->dtype, [&](auto real) {
+    return with_slots(s->n_veh, [&](auto w) {
+      using T = decltype(real);
+      constexpr int NS = decltype(w)::NS, EPW = decltype(w)::EPW;
+      hipLaunchKernelGGL((neighbours_kernel<T, NS, EPW>), dim3((s->n_envs + EPW - 1) / EPW), dim3(NS * EPW),
+                         view_layout<T>(EPW, NS, road->n_lanes).total, st, *s, *road, P, query_lane, front, rear);
+      return launch_status();
+    });
+  });
 }
 
 int ttrl_observe_kinematics_masked(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5639,8 +5657,14 @@ int ttrl_observe_kinematics_masked(const ttrl_state_t* s, const ttrl_lane_table_
   if (rc) return rc < 0 ? rc : TTRL_OK;
   if (!p || !out || check_kin_cfg(s, cfg)) return TTRL_E_ARG;
   hipStream_t st = (hipStream_t)stream;
-  return s->dtype == TTRL_F64 ? dispatch_kin<double>(*s, *road, *p, *cfg, mask, out, ids, st)
-                              : dispatch_kin<float>(*s, *road, *p, *cfg, mask, out, ids, st);
+  return with_real(s->dtype, [&](auto real) {
+    return with_slots(s->n_veh, [&](auto w) {
+      constexpr int NS = decltype(w)::NS, EPW = decltype(w)::EPW;
+      hipLaunchKernelGGL((kinematics_obs_kernel<decltype(real), NS, EPW>), dim3((s->n_envs + EPW - 1) / EPW),
+                         dim3(NS * EPW), 0, st, *s, *road, *p, *cfg, mask, out, ids);
+      return launch_status();
+    });
+  });
 }
 
 int ttrl_observe_kinematics(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5655,16 +5679,13 @@ int ttrl_observe_grid(const ttrl_state_t* s, const ttrl_lane_table_t* road, cons
   if (!p || check_grid_cfg(cfg, out)) return TTRL_E_ARG;
   const size_t lds = grid_scratch_bytes(*cfg, s->n_veh, s->dtype == TTRL_F64 ? 8 : 4);
   if (lds > 160 * 1024) return TTRL_E_UNSUPPORTED;
-  if (s->n_envs == 0) return TTRL_OK;
   hipStream_t st = (hipStream_t)stream;
   // one thread per slot (64 .. 256): smaller blocks for fewer vehicles keep more envs in flight
   // (4096 x 128: 2 waves per env, all 4096 envs resident at once)
   const int nt = s->n_veh <= 64 ? 64 : (s->n_veh <= 128 ? 128 : (s->n_veh <= 192 ? 192 : 256));
-  if (s->dtype == TTRL_F64)
-    hipLaunchKernelGGL(grid_obs_kernel<double>, dim3(s->n_envs), dim3(nt), lds, st, *s, *road, *p, *cfg, out);
-  else
-    hipLaunchKernelGGL(grid_obs_kernel<float>, dim3(s->n_envs), dim3(nt), lds, st, *s, *road, *p, *cfg, out);
-  return launch_status();
+  return launch_real(s->dtype, [&](auto real) {
+    hipLaunchKernelGGL(grid_obs_kernel<decltype(real)>, dim3(s->n_envs), dim3(nt), lds, st, *s, *road, *p, *cfg, out);
+  });
 }
 
 int ttrl_observe_ttc(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5672,18 +5693,14 @@ int ttrl_observe_ttc(const ttrl_state_t* s, const ttrl_lane_table_t* road, const
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
   const bool raw = cfg && cfg->obs_lanes == 0 && cfg->obs_speeds == 0;
-  if (!p || !cfg || !out || cfg->horizon_bins < 1 || cfg->horizon_bins > 64 || (!raw && cfg->obs_lanes < 1) ||
-      (!raw && cfg->obs_speeds < 1) || !(cfg->time_quantization > 0) || p->n_target_speeds < 1 ||
-      p->n_target_speeds > 8)
+  if (!cfg || !out || cfg->horizon_bins < 1 || cfg->horizon_bins > 64 || (!raw && cfg->obs_lanes < 1) ||
+      (!raw && cfg->obs_speeds < 1) || !(cfg->time_quantization > 0) || check_params(p))
     return TTRL_E_ARG;
-  if (s->n_envs == 0) return TTRL_OK;
   const size_t lds = sizeof(int) * p->n_target_speeds * road->n_lanes * cfg->horizon_bins;
   hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == TTRL_F64)
-    hipLaunchKernelGGL(ttc_obs_kernel<double>, dim3(s->n_envs), dim3(64), lds, st, *s, *road, *p, *cfg, out);
-  else
-    hipLaunchKernelGGL(ttc_obs_kernel<float>, dim3(s->n_envs), dim3(64), lds, st, *s, *road, *p, *cfg, out);
-  return launch_status();
+  return launch_real(s->dtype, [&](auto real) {
+    hipLaunchKernelGGL(ttc_obs_kernel<decltype(real)>, dim3(s->n_envs), dim3(64), lds, st, *s, *road, *p, *cfg, out);
+  });
 }
 
 int ttrl_observe_lidar(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5691,29 +5708,30 @@ int ttrl_observe_lidar(const ttrl_state_t* s, const ttrl_lane_table_t* road, con
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
   if (!p || !cfg || !out || cfg->cells < 1 || cfg->cells > 64 || !(cfg->maximum_range > 0)) return TTRL_E_ARG;
-  if (s->n_envs == 0) return TTRL_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == TTRL_F64)
-    hipLaunchKernelGGL(lidar_obs_kernel<double>, dim3(s->n_envs), dim3(64), 0, st, *s, *p, *cfg, out);
-  else
-    hipLaunchKernelGGL(lidar_obs_kernel<float>, dim3(s->n_envs), dim3(64), 0, st, *s, *p, *cfg, out);
-  return launch_status();
+  return launch_real(s->dtype, [&](auto real) {
+    hipLaunchKernelGGL(lidar_obs_kernel<decltype(real)>, dim3(s->n_envs), dim3(64), 0, st, *s, *p, *cfg, out);
+  });
+}
+
+// The three highway resets: the scene's rows from a host-seeded PCG64 state (pcg), or seeded on the
+// device from entropy words (words), for the masked envs or (ar) the finished ones
+static int reset_highway(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
+                         const ttrl_reset_cfg_t* cfg, const uint64_t* pcg, const uint32_t* words, int32_t n_words,
+                         const uint8_t* mask, const AutoReset& ar, void* stream) {
+  if (check_params(p) || check_reset_cfg(s, road, cfg)) return TTRL_E_ARG;
+  return launch_real(s->dtype, [&](auto real) {
+    launch_reset<decltype(real)>(*s, *road, *p, *cfg, (const unsigned long long*)pcg, (unsigned*)words, (int)n_words,
+                                 mask, ar, (hipStream_t)stream);
+  });
 }
 
 int ttrl_reset_highway(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
                        const ttrl_reset_cfg_t* cfg, const uint64_t* pcg, void* stream) {
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!p || !cfg || !pcg || cfg->n_vehicles < 1 || cfg->n_vehicles > s->n_veh || cfg->ego_lane < 0 ||
-      cfg->ego_lane >= road->n_lanes || p->n_target_speeds < 1 || p->n_target_speeds > 8)
-    return TTRL_E_ARG;
-  if (s->n_envs == 0) return TTRL_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == TTRL_F64)
-    launch_reset<double>(*s, *road, *p, *cfg, (const unsigned long long*)pcg, nullptr, 0, nullptr, AutoReset{}, st);
-  else
-    launch_reset<float>(*s, *road, *p, *cfg, (const unsigned long long*)pcg, nullptr, 0, nullptr, AutoReset{}, st);
-  return launch_status();
+  if (!pcg) return TTRL_E_ARG;
+  return reset_highway(s, road, p, cfg, pcg, nullptr, 0, nullptr, AutoReset{}, stream);
 }
 
 int ttrl_reset_highway_seeded(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5721,16 +5739,8 @@ int ttrl_reset_highway_seeded(const ttrl_state_t* s, const ttrl_lane_table_t* ro
                               const uint8_t* mask, void* stream) {
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!p || !cfg || !entropy || n_words < 1 || n_words > 64 || cfg->n_vehicles < 1 || cfg->n_vehicles > s->n_veh ||
-      cfg->ego_lane < 0 || cfg->ego_lane >= road->n_lanes || p->n_target_speeds < 1 || p->n_target_speeds > 8)
-    return TTRL_E_ARG;
-  if (s->n_envs == 0) return TTRL_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == TTRL_F64)
-    launch_reset<double>(*s, *road, *p, *cfg, nullptr, (unsigned*)entropy, (int)n_words, mask, AutoReset{}, st);
-  else
-    launch_reset<float>(*s, *road, *p, *cfg, nullptr, (unsigned*)entropy, (int)n_words, mask, AutoReset{}, st);
-  return launch_status();
+  if (!entropy || n_words < 1 || n_words > 64) return TTRL_E_ARG;
+  return reset_highway(s, road, p, cfg, nullptr, entropy, n_words, mask, AutoReset{}, stream);
 }
 
 int ttrl_auto_reset_highway(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5739,18 +5749,11 @@ int ttrl_auto_reset_highway(const ttrl_state_t* s, const ttrl_lane_table_t* road
                             void* stream) {
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!p || !cfg || !entropy || !terminated || !truncated || !time || !done || n_words < 1 || n_words > 8 ||
-      episode_word < 0 || episode_word >= n_words || cfg->n_vehicles < 1 || cfg->n_vehicles > s->n_veh ||
-      cfg->ego_lane < 0 || cfg->ego_lane >= road->n_lanes || p->n_target_speeds < 1 || p->n_target_speeds > 8)
+  if (!entropy || !terminated || !truncated || !time || !done || n_words < 1 || n_words > 8 || episode_word < 0 ||
+      episode_word >= n_words)
     return TTRL_E_ARG;
-  if (s->n_envs == 0) return TTRL_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const AutoReset ar{terminated, truncated, time, done, episode_word};
-  if (s->dtype == TTRL_F64)
-    launch_reset<double>(*s, *road, *p, *cfg, nullptr, (unsigned*)entropy, (int)n_words, nullptr, ar, st);
-  else
-    launch_reset<float>(*s, *road, *p, *cfg, nullptr, (unsigned*)entropy, (int)n_words, nullptr, ar, st);
-  return launch_status();
+  return reset_highway(s, road, p, cfg, nullptr, entropy, n_words, nullptr,
+                       AutoReset{terminated, truncated, time, done, episode_word}, stream);
 }
 
 int ttrl_seed_pcg64(const uint32_t* entropy, int32_t n_words, uint64_t* state4) {
@@ -5764,9 +5767,7 @@ int ttrl_seed_pcg64(const uint32_t* entropy, int32_t n_words, uint64_t* state4) 
 static int check_ix(const ttrl_state_t* s, const ttrl_lane_table_t* R, const ttrl_params_t* p, const ttrl_ix_cfg_t* c) {
   int rc = check_state(s, R);
   if (rc) return rc;  // EMPTY propagates
-  if (!p || !c || !s->rng || !s->route_road || !s->route_lane || !s->route_n || !s->yielding || !s->reg_steps)
-    return TTRL_E_ARG;
-  if (p->n_target_speeds < 1 || p->n_target_speeds > 8 || c->n_corners != 4) return TTRL_E_ARG;
+  if (!c || !s->rng || !has_net_rows(s) || check_params(p) || c->n_corners != 4) return TTRL_E_ARG;
   if (c->initial_vehicle_count < 1 || c->initial_vehicle_count > TTRL_IX_MAX_INIT || c->warmup_frames < 0)
     return TTRL_E_ARG;
   if (c->ego_lane < 0 || c->ego_lane >= R->n_lanes || c->ego_destination < -1 || c->ego_destination > 3) return TTRL_E_ARG;
@@ -5792,16 +5793,13 @@ int ttrl_ix_reset_parts(const ttrl_state_t* s, const ttrl_lane_table_t* road, co
   if (rc) return rc < 0 ? rc : TTRL_OK;
   if (parts < 0 || parts > 7 || warm_frames < 0) return TTRL_E_ARG;
   if ((parts & TTRL_IX_BEGIN) && (!entropy || n_words < 1 || n_words > 64)) return TTRL_E_ARG;
-  if (s->n_envs == 0) return TTRL_OK;
   hipStream_t st = (hipStream_t)stream;
   const int blocks = s->n_envs;  // one wavefront per env
   if (parts & TTRL_IX_BEGIN) {
-    if (s->dtype == TTRL_F64)
-      hipLaunchKernelGGL(ix_begin_kernel<double>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg,
+    with_real(s->dtype, [&](auto real) {
+      hipLaunchKernelGGL(ix_begin_kernel<decltype(real)>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg,
                          (const unsigned*)entropy, (int)n_words, begin_mask);
-    else
-      hipLaunchKernelGGL(ix_begin_kernel<float>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg,
-                         (const unsigned*)entropy, (int)n_words, begin_mask);
+    });
     if ((rc = launch_status())) return rc;
   }
   // _make_vehicles' warm-up: 3 s of Road.act / Road.step with no controlled vehicle yet; frames
@@ -5809,12 +5807,11 @@ int ttrl_ix_reset_parts(const ttrl_state_t* s, const ttrl_lane_table_t* road, co
   if ((parts & TTRL_IX_WARMUP) && warm_frames > 0 &&
       (rc = run_sim(s, road, p, nullptr, warm_frames, cfg->warmup_dt, MODE_ACT | MODE_STEP, stream, 0, warm_mask)))
     return rc;
-  if (parts & TTRL_IX_FINISH) {
-    if (s->dtype == TTRL_F64)
-      hipLaunchKernelGGL(ix_finish_kernel<double>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg, finish_mask);
-    else
-      hipLaunchKernelGGL(ix_finish_kernel<float>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg, finish_mask);
-  }
+  if (parts & TTRL_IX_FINISH)
+    with_real(s->dtype, [&](auto real) {
+      hipLaunchKernelGGL(ix_finish_kernel<decltype(real)>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg,
+                         finish_mask);
+    });
   return launch_status();
 }
 
@@ -5829,41 +5826,56 @@ int ttrl_ix_reset(const ttrl_state_t* s, const ttrl_lane_table_t* road, const tt
 int ttrl_copy_envs(const ttrl_state_t* dst, const ttrl_state_t* src, const uint8_t* mask, void* stream) {
   if (!dst || !src || !mask) return TTRL_E_ARG;
   if (dst->n_envs != src->n_envs || dst->n_veh != src->n_veh || dst->dtype != src->dtype) return TTRL_E_ARG;
-  if (dst->n_envs < 0 || dst->n_veh < 1 || dst->n_veh > 256 || (dst->dtype != TTRL_F32 && dst->dtype != TTRL_F64))
-    return TTRL_E_ARG;
+  if (!shape_ok(dst)) return TTRL_E_ARG;
   if (dst->n_envs == 0) return TTRL_OK;
-  const void* ptrs[] = {dst->x, dst->y, dst->heading, dst->speed, dst->target_speed, dst->timer, dst->delta, dst->steer,
-                        dst->acc, dst->impact_x, dst->impact_y, dst->lane, dst->target_lane, dst->speed_index,
-                        dst->kind, dst->crashed, dst->has_impact, dst->lane_change, src->x, src->y, src->heading,
-                        src->speed, src->target_speed, src->timer, src->delta, src->steer, src->acc, src->impact_x,
-                        src->impact_y, src->lane, src->target_lane, src->speed_index, src->kind, src->crashed,
-                        src->has_impact, src->lane_change};
-  for (const void* q : ptrs)
-    if (!q) return TTRL_E_ARG;
+  if (check_rows(dst) || check_rows(src)) return TTRL_E_ARG;
   if ((dst->route_road != nullptr) != (src->route_road != nullptr)) return TTRL_E_ARG;
   if (dst->route_road && (!dst->route_lane || !dst->route_n || !dst->yielding || !src->route_lane || !src->route_n ||
                           !src->yielding))
     return TTRL_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (dst->dtype == TTRL_F64)
-    hipLaunchKernelGGL(copy_envs_kernel<double>, dim3(dst->n_envs), dim3(64), 0, st, *dst, *src, mask);
-  else
-    hipLaunchKernelGGL(copy_envs_kernel<float>, dim3(dst->n_envs), dim3(64), 0, st, *dst, *src, mask);
-  return launch_status();
+  return launch_real(dst->dtype, [&](auto real) {
+    hipLaunchKernelGGL(copy_envs_kernel<decltype(real)>, dim3(dst->n_envs), dim3(64), 0, (hipStream_t)stream, *dst,
+                       *src, mask);
+  });
 }
 
 int ttrl_ix_clear_spawn(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
                         const ttrl_ix_cfg_t* cfg, const uint8_t* mask, void* stream) {
   int rc = check_ix(s, road, p, cfg);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (s->n_envs == 0) return TTRL_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int blocks = s->n_envs;  // one wavefront per env
-  if (s->dtype == TTRL_F64)
-    hipLaunchKernelGGL(ix_clear_spawn_kernel<double>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg, mask);
-  else
-    hipLaunchKernelGGL(ix_clear_spawn_kernel<float>, dim3(blocks), dim3(64), 0, st, *s, *road, *p, *cfg, mask);
-  return launch_status();
+  return launch_real(s->dtype, [&](auto real) {  // one wavefront per env
+    hipLaunchKernelGGL(ix_clear_spawn_kernel<decltype(real)>, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, *s,
+                       *road, *p, *cfg, mask);
+  });
+}
+
+// The scenes reset ahead of time and their bookkeeping (ttrl_ix_step_tail, ttrl_ix_env_step): K in
+// [2, 16] spare rows per env of s's shape and dtype, with every row an intersection state needs.
+// s holds at least one env (check_ix returned TTRL_OK, not EMPTY).
+static int check_spare(const ttrl_state_t* s, const ttrl_state_t* spare, const uint8_t* spare_parity,
+                       const uint32_t* entropy, const uint32_t* spare_entropy, int32_t n_words, const uint8_t* done,
+                       const uint8_t* spare_mask, int* K) {
+  if (!spare || !spare_parity || !entropy || !spare_entropy || n_words < 1 || n_words > 65 || !done || !spare_mask)
+    return TTRL_E_ARG;
+  *K = spare->n_envs / s->n_envs;
+  if (*K < 2 || *K > 16 || spare->n_envs != *K * s->n_envs || spare->n_veh != s->n_veh || spare->dtype != s->dtype ||
+      !spare->rng || !has_net_rows(spare))
+    return TTRL_E_ARG;
+  return check_rows(spare);
+}
+
+// The dispatch order groups the envs of one simulate workgroup (EPW: 2 on 32 slots, else 1), so it
+// is kept only when the caller gives `order` and the groups divide the batch.  order_live: where
+// the tail then leaves each env's live vehicles (order's second half; null: no order) ...
+static int order_group(const ttrl_state_t* s) { return slots_for(s->n_veh) == 32 ? 2 : 1; }
+static int32_t* order_live(const ttrl_state_t* s, int32_t* order) {
+  return order && s->n_envs % order_group(s) == 0 ? order + s->n_envs : nullptr;
+}
+// ... and launch_order: the next step's dispatch order from them (ix_order_kernel), after the tail.
+static void launch_order(const ttrl_state_t* s, int32_t* order, hipStream_t st) {
+  if (!order_live(s, order)) return;
+  const int G = order_group(s);
+  hipLaunchKernelGGL(ix_order_kernel, dim3(1), dim3(1024), 0, st, order, s->n_envs, G, G * s->n_veh);
 }
 
 int ttrl_ix_step_tail(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
@@ -5874,42 +5886,28 @@ int ttrl_ix_step_tail(const ttrl_state_t* s, const ttrl_lane_table_t* road, cons
                       int32_t* obs_ids_out, int64_t* live_count, int32_t* order, void* stream) {
   int rc = check_ix(s, road, p, cfg);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!spare || !terminated || !truncated || !spare_parity || !entropy || !spare_entropy || n_words < 1 ||
-      n_words > 65 || !time || !done || !spare_mask)
+  int K = 0;
+  if (!terminated || !truncated || !time ||
+      check_spare(s, spare, spare_parity, entropy, spare_entropy, n_words, done, spare_mask, &K))
     return TTRL_E_ARG;
-  const int K = s->n_envs > 0 ? spare->n_envs / s->n_envs : 0;
-  if (K < 2 || K > 16 || spare->n_envs != K * s->n_envs || spare->n_veh != s->n_veh || spare->dtype != s->dtype || !spare->rng ||
-      !spare->reg_steps || !spare->route_road || !spare->route_lane || !spare->route_n || !spare->yielding)
-    return TTRL_E_ARG;
-  const void* sp[] = {spare->x, spare->y, spare->heading, spare->speed, spare->target_speed, spare->timer,
-                      spare->delta, spare->steer, spare->acc, spare->impact_x, spare->impact_y, spare->lane,
-                      spare->target_lane, spare->speed_index, spare->kind, spare->crashed, spare->has_impact,
-                      spare->lane_change};
-  for (const void* q : sp)
-    if (!q) return TTRL_E_ARG;
   if (obs_cfg) {  // the re-observation puts one slot on each lane of the env's wavefront
-    if (check_kin_cfg(s, obs_cfg) || !obs_in || !obs_out || (!obs_ids_in) != (!obs_ids_out) || s->n_veh > 64)
-      return obs_cfg && s->n_veh > 64 ? TTRL_E_UNSUPPORTED : TTRL_E_ARG;
+    if (s->n_veh > 64) return TTRL_E_UNSUPPORTED;
+    if (check_kin_cfg(s, obs_cfg) || !obs_in || !obs_out || (!obs_ids_in) != (!obs_ids_out)) return TTRL_E_ARG;
   }
   IxTail t{};
   t.spare = *spare; t.K = K; t.term = terminated; t.trunc = truncated; t.par = spare_parity; t.ent = entropy;
   t.spare_ent = spare_entropy; t.nw = n_words; t.time = time; t.done = done; t.spare_mask = spare_mask;
   t.live = reinterpret_cast<unsigned long long*>(live_count);
-  // the dispatch order groups the envs of one simulate workgroup (EPW: 2 on 32 slots, else 1)
-  const int G = slots_for(s->n_veh) == 32 ? 2 : 1;
-  const bool ordered = order && s->n_envs % G == 0;
-  if (ordered) t.live_env = order + s->n_envs;
+  t.live_env = order_live(s, order);
   if (obs_cfg) {
     t.kcfg = *obs_cfg; t.obs = true; t.obs_in = obs_in; t.obs_out = obs_out; t.ids_in = obs_ids_in;
     t.ids_out = obs_ids_out;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == TTRL_F64)
-    hipLaunchKernelGGL(ix_step_tail_kernel<double>, dim3(s->n_envs), dim3(64), 0, st, *s, *road, *p, *cfg, t);
-  else
-    hipLaunchKernelGGL(ix_step_tail_kernel<float>, dim3(s->n_envs), dim3(64), 0, st, *s, *road, *p, *cfg, t);
-  if (ordered)
-    hipLaunchKernelGGL(ix_order_kernel, dim3(1), dim3(1024), 0, st, order, s->n_envs, G, G * s->n_veh);
+  with_real(s->dtype, [&](auto real) {
+    hipLaunchKernelGGL(ix_step_tail_kernel<decltype(real)>, dim3(s->n_envs), dim3(64), 0, st, *s, *road, *p, *cfg, t);
+  });
+  launch_order(s, order, st);
   return launch_status();
 }
 
@@ -5923,34 +5921,14 @@ int ttrl_ix_env_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, const
                      const int32_t* action_lut, int32_t n_action_lut, int64_t* live_count, void* stream) {
   int rc = check_ix(s, road, p, cfg);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!spare || !spare_parity || !entropy || !spare_entropy || n_words < 1 || n_words > 65 || !done || !spare_mask)
+  int K = 0;
+  if (check_spare(s, spare, spare_parity, entropy, spare_entropy, n_words, done, spare_mask, &K) || !obs_next ||
+      (!obs_ids) != (!ids_next))
     return TTRL_E_ARG;
-  const int K = spare->n_envs / s->n_envs;
-  if (K < 2 || K > 16 || spare->n_envs != K * s->n_envs || spare->n_veh != s->n_veh || spare->dtype != s->dtype ||
-      !spare->rng || !spare->reg_steps || !spare->route_road || !spare->route_lane || !spare->route_n || !spare->yielding)
-    return TTRL_E_ARG;
-  {
-    const void* sp[] = {spare->x, spare->y, spare->heading, spare->speed, spare->target_speed, spare->timer,
-                        spare->delta, spare->steer, spare->acc, spare->impact_x, spare->impact_y, spare->lane,
-                        spare->target_lane, spare->speed_index, spare->kind, spare->crashed, spare->has_impact,
-                        spare->lane_change};
-    for (const void* q : sp)
-      if (!q) return TTRL_E_ARG;
-  }
-  if (!obs_cfg || !obs || !obs_next || check_kin_cfg(s, obs_cfg) || (!obs_ids) != (!ids_next)) return TTRL_E_ARG;
-  if (!reward_cfg || !time || !reward || !terminated || !truncated || (!ego_speed) != (!ego_crashed))
-    return TTRL_E_ARG;
-  if (n_action_lut < 0 || n_action_lut > 8 || (n_action_lut > 0 && !action_lut)) return TTRL_E_ARG;
-  if (slots_for(s->n_veh) > 64) return TTRL_E_UNSUPPORTED;  // the fused tail needs one wavefront per workgroup
-  StepOut so{};
-  for (int q = 0; q < n_action_lut; ++q) {
-    if (action_lut[q] < TTRL_LANE_LEFT || action_lut[q] > TTRL_SLOWER) return TTRL_E_ARG;
-    so.lut[q] = (int8_t)action_lut[q];
-  }
-  so.n_lut = n_action_lut;
-  so.kcfg = *obs_cfg; so.obs = obs; so.ids = obs_ids;
-  so.rcfg = *reward_cfg; so.time = time; so.time_inc = time_inc; so.reward = reward; so.term = terminated;
-  so.trunc = truncated; so.comp = components; so.ego_speed = ego_speed; so.ego_crashed = ego_crashed;
+  StepOut so{};  // observation and step tail both required; the fused tail needs one wavefront per workgroup
+  if ((rc = fill_step_out(so, s, true, obs_cfg, obs, obs_ids, true, reward_cfg, time, time_inc, reward, terminated,
+                          truncated, components, ego_speed, ego_crashed, action_lut, n_action_lut, 64)))
+    return rc;
   so.order = order;
   IxEpi ie{};
   ie.C = *cfg;
@@ -5959,19 +5937,16 @@ int ttrl_ix_env_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, const
   ie.live = reinterpret_cast<unsigned long long*>(live_count);
   ie.spare = *spare; ie.K = K; ie.par = spare_parity; ie.ent = entropy; ie.spare_ent = spare_entropy;
   ie.nw = n_words; ie.done = done; ie.spare_mask = spare_mask;
-  const int G = slots_for(s->n_veh) == 32 ? 2 : 1;  // envs per wavefront (the dispatch order's groups)
-  const bool ordered = order && s->n_envs % G == 0;
-  if (ordered) ie.live_env = order + s->n_envs;  // ix_order_kernel's input
+  ie.live_env = order_live(s, order);  // ix_order_kernel's input
   hipStream_t st = (hipStream_t)stream;
-  if (s->dtype == TTRL_F64)
-    rc = G == 2 ? launch_sim_ix<double, 32, 2>(*s, *road, *p, actions, frames, dt, st, so, ie)
-                : launch_sim_ix<double, 64, 1>(*s, *road, *p, actions, frames, dt, st, so, ie);
-  else
-    rc = G == 2 ? launch_sim_ix<float, 32, 2>(*s, *road, *p, actions, frames, dt, st, so, ie)
-                : launch_sim_ix<float, 64, 1>(*s, *road, *p, actions, frames, dt, st, so, ie);
+  const bool pair = slots_for(s->n_veh) == 32;  // two envs per wavefront
+  rc = with_real(s->dtype, [&](auto real) {
+    using T = decltype(real);
+    return pair ? launch_sim_ix<T, 32, 2>(*s, *road, *p, actions, frames, dt, st, so, ie)
+                : launch_sim_ix<T, 64, 1>(*s, *road, *p, actions, frames, dt, st, so, ie);
+  });
   if (rc) return rc;
-  if (ordered)  // the next step's dispatch order, as ttrl_ix_step_tail writes it
-    hipLaunchKernelGGL(ix_order_kernel, dim3(1), dim3(1024), 0, st, order, s->n_envs, G, G * s->n_veh);
+  launch_order(s, order, st);  // the next step's dispatch order, as ttrl_ix_step_tail writes it
   return launch_status();
 }
 
@@ -5980,16 +5955,13 @@ int ttrl_rewards_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, cons
                       float* components, void* ego_speed, uint8_t* ego_crashed, void* stream) {
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
-  if (!cfg || !time || !reward || !terminated || !truncated || (!ego_speed) != (!ego_crashed)) return TTRL_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
+  if (!cfg || !reward_out_ok(time, reward, terminated, truncated, ego_speed, ego_crashed)) return TTRL_E_ARG;
   const int blocks = (s->n_envs + 255) / 256;
-  if (s->dtype == TTRL_F64)
-    hipLaunchKernelGGL(rewards_kernel<double>, dim3(blocks), dim3(256), 0, st, *s, *road, *cfg, time, time_inc,
-                       reward, terminated, truncated, components, (double*)ego_speed, ego_crashed);
-  else
-    hipLaunchKernelGGL(rewards_kernel<float>, dim3(blocks), dim3(256), 0, st, *s, *road, *cfg, time, time_inc,
-                       reward, terminated, truncated, components, (float*)ego_speed, ego_crashed);
-  return launch_status();
+  return launch_real(s->dtype, [&](auto real) {
+    using T = decltype(real);
+    hipLaunchKernelGGL(rewards_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *s, *road, *cfg, time,
+                       time_inc, reward, terminated, truncated, components, (T*)ego_speed, ego_crashed);
+  });
 }
 
 int ttrl_rewards_ex(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_reward_cfg_t* cfg,
