@@ -309,7 +309,11 @@ int ttrl_env_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, const tt
 /* ttrl_env_step with an OccupancyGridObservation (observation.py:353-483) of the final state
  * instead of the Kinematics one: grid [E][F][shape_x][shape_y] float32, as ttrl_observe_grid
  * writes it after ttrl_env_step.  On a straight road of 64 / 128 vehicle slots the step's own
- * launch writes it from its LDS view (one launch); elsewhere the two launches run in turn. */
+ * launch writes it from its LDS view (one launch) when the grid's scratch fits that launch's
+ * LDS block (64 KB at most, e.g. 3 x 64 x 64 cells); elsewhere, and for a larger grid, the two
+ * launches run in turn.  A grid beyond ttrl_observe_grid's own cap (160 KB of scratch, about
+ * 198 x 198 cells) returns TTRL_E_UNSUPPORTED before anything is launched: the state is not
+ * stepped. */
 int ttrl_env_step_grid(const ttrl_state_t* s, const ttrl_lane_table_t* road, const ttrl_params_t* p,
                        const int32_t* actions, int32_t frames, double dt,
                        const ttrl_grid_cfg_t* grid_cfg, float* grid,

@@ -18,6 +18,11 @@ with the two configurations per class that ``gen_golden.py`` records.  Each outp
 restated one bit for bit (asserted here); ``tests/golden/obsref_<scene>.npz`` keeps the reference
 outputs so that ``tests/test_oracle_golden.py`` can hold the committed fixtures to them.
 
+``replay_grids`` records ``OccupancyGridObservation.observe`` alone under the configurations of
+``oracle/grid_cases.py`` (non-square, unclipped, partial ranges, on_road at 256 and 147 cells,
+128 x 128) on four of the scenes: ``tests/golden/obsref_grid_<scene>.npz``, float32.  These have no
+restatement in ``gen_golden.py``; the oracle and the HIP kernels are held to them directly.
+
 Stand-ins.  ``observation.py`` imports ``gymnasium.spaces`` (``Box`` / ``Space`` for ``space()``)
 and, through ``ttrl_env.envs.common.graphics`` (the ``EnvViewer`` it names for the grayscale
 observation), ``pygame`` and ``gymnasium``-typed action classes.  None of them is on the computed
@@ -41,6 +46,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import gen_golden as G  # noqa: E402  (imports the reference sim core, no stand-ins)
+from grid_cases import GRID_CASES, GRID_SCENES, GRID_SHAPES, scene_name  # noqa: E402
 
 OUT = G.OUT
 
@@ -110,11 +116,23 @@ def restated(road):
     return o
 
 
-def replay(road, policy_steps: int, seed: int):
+def frames(road, policy_steps: int, seed: int, observe):
     """gen_golden.rollout's frame loop (same action draw), observing after reset and after each
-    policy step with the reference classes."""
+    policy step."""
     rng = np.random.default_rng(7777 + seed)
     actions = rng.integers(0, 5, size=policy_steps).astype(np.int32)
+    observe()
+    for p in range(policy_steps):
+        for f in range(15):
+            if f == 0:
+                road.vehicles[0].act(G.ACTIONS_ALL[int(actions[p])])
+            road.act()
+            road.step(1 / 15)
+        observe()
+
+
+def replay(road, policy_steps: int, seed: int):
+    """The scene's policy steps observed with the reference classes."""
     obs = observers(road)
     out = {k: [] for k in CLASS_CFGS}
 
@@ -126,14 +144,34 @@ def replay(road, policy_steps: int, seed: int):
             assert np.array_equal(ref.astype(mine[k].dtype), mine[k]), k  # restatement == reference
             out[k].append(ref)
 
-    observe()
-    for p in range(policy_steps):
-        for f in range(15):
-            if f == 0:
-                road.vehicles[0].act(G.ACTIONS_ALL[int(actions[p])])
-            road.act()
-            road.step(1 / 15)
-        observe()
+    frames(road, policy_steps, seed, observe)
+    return {k: np.stack(v) for k, v in out.items()}
+
+
+def replay_grids(road, policy_steps: int, seed: int):
+    """The scene's policy steps observed by the reference OccupancyGridObservation under
+    grid_cases.GRID_CASES (non-square, unclipped, partial ranges, on_road at both write-outs, a
+    128 x 128 grid), float32 [steps + 1, F, W, H] per case.  No fixture may be vacuous: every
+    observation has at least two occupied cells besides the observer's, and every on_road layer has
+    cells on and off the road."""
+    env = types.SimpleNamespace(road=road, vehicle=road.vehicles[0], PERCEPTION_DISTANCE=5.0 * G.R.Vehicle.MAX_SPEED,
+                                config={"policy_frequency": 1}, np_random=np.random.default_rng(0))
+    obs = {k: O.OccupancyGridObservation(env, **cfg) for k, cfg in GRID_CASES.items()}
+    out = {k: [] for k in GRID_CASES}
+
+    def observe():
+        for k, ob in obs.items():
+            feats = GRID_CASES[k]["features"]
+            ref = np.asarray(ob.observe())
+            assert ref.shape == GRID_SHAPES[k], (k, ref.shape)
+            got = ref.astype(np.float32)
+            assert np.array_equal(got.astype(ref.dtype), ref), k  # float32 holds the reference's values
+            assert int((got[feats.index("presence")] != 0).sum()) >= 3, (k, "fewer than two other vehicles in view")
+            road_layer = got[feats.index("on_road")] if "on_road" in feats else None
+            assert road_layer is None or (road_layer.min() == 0 and road_layer.max() == 1), (k, "on_road is uniform")
+            out[k].append(got)
+
+    frames(road, policy_steps, seed, observe)
     return {k: np.stack(v) for k, v in out.items()}
 
 
@@ -181,6 +219,12 @@ def main():
         name = f"{kind}_n{n}_s{seed}"
         np.savez_compressed(os.path.join(OUT, "obsref_" + name + ".npz"), **d)
         print(name, {k: v.shape for k, v in d.items()})
+    for kind, n, seed, steps in GRID_SCENES:
+        road = (G.make_highway(n, seed) if kind == "highway" else
+                G.make_dense(n, seed) if kind == "dense" else G.make_curved(kind, n, seed))
+        d = replay_grids(road, steps, seed)
+        np.savez_compressed(os.path.join(OUT, "obsref_grid_" + scene_name(kind, n, seed) + ".npz"), **d)
+        print("grid", scene_name(kind, n, seed), {k: v.shape for k, v in d.items()})
 
 
 if __name__ == "__main__":

@@ -370,12 +370,13 @@ def _fault_cases(blob):
                 for name, m in grid:
                     add(e, w + name, _both(_n_veh(nv), m))
 
-    # ---- a grid beyond the LDS caps: 160 KB of scratch alone, 64 KB over the fused step's view
+    # ---- a grid beyond the LDS cap, 160 KB of scratch: refused by the observer and, before it steps,
+    # by the fused step (a grid over the fused launch's 64 KB takes two launches: tests/test_gpu_grid.py)
     add("ttrl_observe_grid", "200 x 200 cells", _both(_set("grid_cfg", "shape_x", 200), _set("grid_cfg", "shape_y", 200)),
         E_UNSUPPORTED)
     for nv in (64, 100):
-        add("ttrl_env_step_grid", f"n_veh {nv}, 128 x 128 cells",
-            _both(_n_veh(nv), _set("grid_cfg", "shape_x", 128), _set("grid_cfg", "shape_y", 128)), E_UNSUPPORTED)
+        add("ttrl_env_step_grid", f"n_veh {nv}, 200 x 200 cells",
+            _both(_n_veh(nv), _set("grid_cfg", "shape_x", 200), _set("grid_cfg", "shape_y", 200)), E_UNSUPPORTED)
     add("ttrl_diag_simulate", "ablate in a product build", _arg(ablate=1), E_UNSUPPORTED)
     add("ttrl_diag_simulate", "ablate, s null", _arg(ablate=1, s=None), E_UNSUPPORTED)
     add("ttrl_meta_action", "actions null", _arg(actions=None))

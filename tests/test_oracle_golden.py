@@ -4,13 +4,15 @@ unmodified reference (oracle/gen_golden.py).  CPU only.
 Pinned here: Road.act/Road.step per frame (positions/speeds/headings to 1e-12, every
 discrete field exact), the fused 15-frame policy step, Road.neighbour_vehicles,
 Kinematics (5x5 default, 15x7 env.json) and OccupancyGrid (7x32x32 dense, 4x11x11 on_road)
-observations bit-identical, TimeToCollision exact and Lidar to float32 rounding, and the
+observations bit-identical (and the OccupancyGrid on non-square, unclipped, on_road and
+128 x 128 grids against the reference observer's own output), TimeToCollision exact and Lidar to float32 rounding, and the
 numpy-PCG64 scene generator bit-identical.
 """
 import numpy as np
 import pytest
 
 from conftest import golden_files, load_golden, scene_files
+from oracle.grid_cases import GRID_CASES, GRID_SCENES, GRID_SHAPES, scene_name
 from oracle.oracle import HostState, Oracle
 from topotrafficrl_amd import _abi
 
@@ -149,6 +151,24 @@ def test_observation_fixtures_equal_the_reference_observers(name, cases):
     for k in ("kin5", "kin15", "grid7", "grid_onroad", "ttc", "lidar"):
         assert ref[k].shape == d[k].shape, k
         assert np.array_equal(ref[k].astype(d[k].dtype), d[k]), k
+
+
+@pytest.mark.parametrize("case", list(GRID_CASES))
+@pytest.mark.parametrize("scene", [scene_name(k, n, s) for k, n, s, _ in GRID_SCENES])
+def test_grid_shapes_equal_the_reference_observer(scene, case, cases):
+    """Oracle.observe_grid on grids that are not square (a transposed cell index or stride shows),
+    unclipped, with ranges for some features only, with an on_road layer at 256 cells (a multiple of
+    4) and at 147, and at 128 x 128 cells == the reference OccupancyGridObservation.observe on every
+    policy step of the scene, bit for bit (oracle/grid_cases.py, gen_golden_obs.py::replay_grids)."""
+    d = cases[scene]
+    ref = load_golden(golden_files(f"obsref_grid_{scene}.npz")[0])[case]
+    steps = int(d["meta"][2])
+    assert ref.dtype == np.float32 and ref.shape == (steps + 1,) + GRID_SHAPES[case]
+    o = Oracle(_abi.lane_table_from_arrays(d["lane_table"]), P)
+    cfg = _abi.grid_cfg(**GRID_CASES[case])
+    for p in range(steps + 1):
+        got = o.observe_grid(HostState.from_golden(d, 15 * p), cfg)[0]
+        assert np.array_equal(got, ref[p]), (p, np.argwhere(got != ref[p])[:5])
 
 
 @pytest.mark.parametrize("seed", range(6))

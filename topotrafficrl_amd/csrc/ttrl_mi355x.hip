@@ -5462,18 +5462,34 @@ int launch_sim_ix(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_
 // ttrl_env_step_grid's launch: the straight one-env instance (sorted view) with the OccupancyGrid
 // epilogue, its scratch over the view's blocks dead after the last frame (the own-state and the
 // frame-transient blocks: 8.8 KB per float64 128-slot env for the 8 KB a 7 x 32 x 32 grid and its
-// cfg need; the block grows if a grid needs more)
+// cfg need; the block grows if a grid needs more).  fused_grid_lds: the launch's LDS bytes, or 0
+// when the block would pass FUSED_GRID_LDS_CAP (or the tail's scratch does not fit): ttrl_env_step_grid
+// then takes its two launches.
+constexpr size_t FUSED_GRID_LDS_CAP = 64 * 1024;
+// ttrl_observe_grid's scratch cap: the CU's 160 KB of LDS
+constexpr size_t GRID_LDS_CAP = 160 * 1024;
+template <typename T, int NS>
+size_t fused_grid_lds(const ttrl_grid_cfg_t& cfg, int n_veh, uint32_t* scr = nullptr) {
+  const ViewLayout o = view_layout<T>(1, NS, STRAIGHT_LANE_CAP, false, true);
+  if (!tail_fits<T>(o, 1, NS)) return 0;
+  if (scr) *scr = (uint32_t)o.own;
+  const size_t need = o.own + ((sizeof(ttrl_grid_cfg_t) + 15) & ~(size_t)15) + grid_scratch_bytes(cfg, n_veh, sizeof(T));
+  const size_t lds = need > o.total ? (need + 15) & ~(size_t)15 : o.total;
+  return lds > FUSED_GRID_LDS_CAP ? 0 : lds;
+}
+size_t fused_grid_lds(int dtype, int slots, const ttrl_grid_cfg_t& cfg, int n_veh) {
+  if (slots != 64 && slots != 128) return 0;
+  return with_real(dtype, [&](auto real) {
+    using T = decltype(real);
+    return slots == 128 ? fused_grid_lds<T, 128>(cfg, n_veh) : fused_grid_lds<T, 64>(cfg, n_veh);
+  });
+}
 template <typename T, int NS>
 int launch_sim_grid(const ttrl_state_t& s, const ttrl_lane_table_t& R, const ttrl_params_t& P, const int32_t* actions,
                     int frames, double dt, hipStream_t stream, const StepOut& ob, GridEpi ge) {
   if (s.n_envs == 0) return TTRL_OK;
-  const ViewLayout o = view_layout<T>(1, NS, STRAIGHT_LANE_CAP, false, true);
-  if (!tail_fits<T>(o, 1, NS)) return TTRL_E_UNSUPPORTED;
-  ge.scr = (uint32_t)o.own;
-  const size_t need =
-      o.own + ((sizeof(ttrl_grid_cfg_t) + 15) & ~(size_t)15) + grid_scratch_bytes(ge.cfg, s.n_veh, sizeof(T));
-  const size_t lds = need > o.total ? (need + 15) & ~(size_t)15 : o.total;
-  if (lds > 64 * 1024) return TTRL_E_UNSUPPORTED;
+  const size_t lds = fused_grid_lds<T, NS>(ge.cfg, s.n_veh, &ge.scr);
+  if (!lds) return TTRL_E_UNSUPPORTED;  // ttrl_env_step_grid asks fused_grid_lds first
   hipLaunchKernelGGL((simulate_grid_kernel<T, NS>), dim3(s.n_envs), dim3(NS), lds, stream, s, R, params_for<T>(P),
                      actions, frames, dt, ob, ge);
   return launch_status();
@@ -5549,7 +5565,12 @@ int ttrl_env_step_grid(const ttrl_state_t* s, const ttrl_lane_table_t* road, con
   int rc = check_state(s, road);
   if (rc) return rc < 0 ? rc : TTRL_OK;
   if (check_grid_cfg(grid_cfg, grid)) return TTRL_E_ARG;
-  if (!grid_fusable(*s, *road)) {  // two launches: the step, then grid_obs_kernel
+  // a grid beyond ttrl_observe_grid's cap is refused before anything is launched: no stepped
+  // state without its observation
+  if (grid_scratch_bytes(*grid_cfg, s->n_veh, s->dtype == TTRL_F64 ? 8 : 4) > GRID_LDS_CAP) return TTRL_E_UNSUPPORTED;
+  // two launches (the step, then grid_obs_kernel): another road or slot class, or a grid whose
+  // scratch does not fit the fused launch's LDS block
+  if (!grid_fusable(*s, *road) || !fused_grid_lds(s->dtype, slots_for(s->n_veh), *grid_cfg, s->n_veh)) {
     rc = ttrl_env_step(s, road, p, actions, frames, dt, nullptr, nullptr, nullptr, reward_cfg, time, time_inc, reward,
                        terminated, truncated, components, ego_speed, ego_crashed, nullptr, action_lut, n_action_lut,
                        stream);
@@ -5590,6 +5611,15 @@ int ttrl_env_step(const ttrl_state_t* s, const ttrl_lane_table_t* road, const tt
 /* Diagnostic only (not in include/): the simulate kernel's LDS view bytes per workgroup. */
 long ttrl_diag_view_bytes(int32_t dtype, int32_t epw, int32_t ns, int32_t n_lanes, int32_t graph, int32_t sorted) {
   return (long)host_view_bytes(dtype, epw, ns, n_lanes, graph != 0, sorted != 0);
+}
+
+/* Diagnostic only (not in include/): the LDS bytes per workgroup ttrl_env_step_grid's fused launch
+ * requests for a state of this dtype, slot class (64 or 128) and n_veh on a straight road with this
+ * grid; 0: the grid does not fit it (or the slot class has no fused launch) and the entry point
+ * takes two launches. */
+long ttrl_diag_grid_step_lds(int32_t dtype, int32_t slots, const ttrl_grid_cfg_t* cfg, int32_t n_veh) {
+  if (!cfg || (dtype != TTRL_F32 && dtype != TTRL_F64) || n_veh < 1 || n_veh > slots) return 0;
+  return (long)fused_grid_lds(dtype, slots, *cfg, n_veh);
 }
 
 /* Diagnostic only (not in include/): the flattened enforcement's queue capacity of a road-network
@@ -5678,7 +5708,7 @@ int ttrl_observe_grid(const ttrl_state_t* s, const ttrl_lane_table_t* road, cons
   if (rc) return rc < 0 ? rc : TTRL_OK;
   if (!p || check_grid_cfg(cfg, out)) return TTRL_E_ARG;
   const size_t lds = grid_scratch_bytes(*cfg, s->n_veh, s->dtype == TTRL_F64 ? 8 : 4);
-  if (lds > 160 * 1024) return TTRL_E_UNSUPPORTED;
+  if (lds > GRID_LDS_CAP) return TTRL_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   // one thread per slot (64 .. 256): smaller blocks for fewer vehicles keep more envs in flight
   // (4096 x 128: 2 waves per env, all 4096 envs resident at once)
