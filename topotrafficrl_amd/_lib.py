@@ -4,7 +4,7 @@ The product calls the library through the PyTorch operators of ops.py (lib/libtt
 linked against it); this loader checks the ABI version and the exported symbols, and serves the
 ABI tests and the kernel-timing tools.  There is no fallback: if the library is missing or fails
 to load, every product entry point raises.  Build it with ``python -c "import __graft_entry__ as g; g.build()"``
-or ``python -m topotrafficrl_amd.build``.
+(or ``python __graft_entry__.py``).
 """
 from __future__ import annotations
 
@@ -55,6 +55,15 @@ _SIGS = {
                                 C.c_uint64, C.c_int64, _P, C.c_int64, _P, _P, _P, _P], C.c_int),
 }
 EXPORTS = [k for k in _SIGS]
+# include/ttrl_qnet.h: the fused MLP / dueling Q-network forward (an addition to the same library)
+_I32 = C.c_int32
+QNET_SIGS = {
+    "ttrl_mlp_sizes": ([_I32, _I32, _P, _I32, _I32], C.c_int64),
+    "ttrl_mlp_q": ([_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P], C.c_int),
+    "ttrl_mlp_act": ([_P, _I32, _I32, _I32, _P, _P, _I32, _I32, C.c_float, _P, C.c_uint64, C.c_int64, _P, C.c_int64,
+                      _P, _P, _P, _P], C.c_int),
+}
+QNET_EXPORTS = [k for k in QNET_SIGS]
 
 _lib = None
 
@@ -76,7 +85,7 @@ def load(path: str | None = None, check_abi: bool = True) -> C.CDLL:
     if not os.path.exists(p):
         raise ImportError(f"HIP library not built: {p} (run __graft_entry__.build())")
     lib = C.CDLL(p)
-    for name, (args, res) in _SIGS.items():
+    for name, (args, res) in {**_SIGS, **QNET_SIGS}.items():
         fn = getattr(lib, name, None)
         if fn is None:
             if path is None:

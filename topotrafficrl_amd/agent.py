@@ -9,6 +9,12 @@ scripts/configs/IntersectionEnv/agents/DQNAgent/baseline.json:12-17).  The forwa
 dense contraction (7->64->64 embeddings, 2-head attention over 15 entities, 64->64->64->n
 head): it runs as torch GEMMs on the same HIP stream as the simulator (hipBLASLt/MFMA),
 no host round trip between env.step and the next action.
+
+The other value nets of models.model_factory (:431-441) are restated too, with the reference's
+state-dict names: MultiLayerPerceptron with its activation (baseline.json, grid.json),
+DuelingNetwork (:79-104) and ConvolutionalNetwork (:107-154, grid_convnet.json); ``model_factory``
+sizes them from the observation shape as size_model_config (:404-428) does and ``QNetworkPolicy``
+acts with them, through the fused MLP forward (ttrl::mlp_act) where it covers the network.
 """
 from __future__ import annotations
 
@@ -29,20 +35,178 @@ EGO_ATTENTION_2H = {  # configs/IntersectionEnv/agents/DQNAgent/ego_attention.js
 }
 
 
-class MultiLayerPerceptron(nn.Module):
-    def __init__(self, inp: int, layers, out: int | None = None, reshape: bool = False):
+def activation_factory(activation_type: str):
+    """models.py:391-397"""
+    if activation_type == "RELU":
+        return F.relu
+    if activation_type == "TANH":
+        return torch.tanh
+    raise ValueError(f"Unknown activation_type: {activation_type}")
+
+
+def xavier_reset(module: nn.Module, generator: torch.Generator | None = None) -> nn.Module:
+    """BaseModule._init_weights (models.py:24-33) over every Linear / Conv2d: Xavier-uniform weights,
+    zero biases, drawn from ``generator``."""
+    for m in module.modules():
+        if isinstance(m, (nn.Linear, nn.Conv2d)):
+            fan_in, fan_out = nn.init._calculate_fan_in_and_fan_out(m.weight)
+            bound = math.sqrt(6.0 / (fan_in + fan_out))
+            with torch.no_grad():
+                m.weight.uniform_(-bound, bound, generator=generator)
+                if m.bias is not None:
+                    m.bias.zero_()
+    return module
+
+
+def _mlp_in_kernel_domain(layers, n_out: int) -> bool:
+    """The sizes ttrl_mlp_q covers (include/ttrl_qnet.h); ``n_out``: the head's columns."""
+    return (1 <= len(layers) <= 3 and 1 <= layers[0].in_features <= 1024 and 1 <= n_out <= 16
+            and all(lin.out_features % 16 == 0 and 16 <= lin.out_features <= 128 for lin in layers))
+
+
+class _FusedMlp:
+    """packed_weights / fused_q of the value nets the fused MLP forward covers (ttrl::mlp_q):
+    subclasses give ``_fused_parts()`` = (hidden Linear layers, head Linear layers, dueling)."""
+
+    def reset(self, generator: torch.Generator | None = None):
+        return xavier_reset(self, generator)
+
+    def fused_spec(self):
+        """(widths, n_actions, dueling) as ttrl::mlp_q / ttrl::mlp_act take them."""
+        layers, heads, dueling = self._fused_parts()
+        return [lin.out_features for lin in layers], heads[0].out_features, dueling
+
+    def packed_weights(self) -> torch.Tensor:
+        """The weights in the ttrl_mlp_q packed layout (include/ttrl_qnet.h), cached until a
+        parameter changes (optimizer steps bump the tensors' versions)."""
+        layers, heads, _ = self._fused_parts()
+        tensors = [t for lin in list(layers) + list(heads) for t in (lin.weight, lin.bias)]
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        if getattr(self, "_packed_key", None) != key:
+            # matrices as [in][out]; a dueling head is one [last][A + 1] matrix, the value column last
+            parts = [t.detach().t().reshape(-1) if t.dim() == 2 else t.detach() for lin in layers
+                     for t in (lin.weight, lin.bias)]
+            parts.append(torch.cat([h.weight.detach().t() for h in heads], dim=1).reshape(-1))
+            parts.append(torch.cat([h.bias.detach() for h in heads]))
+            self._packed = torch.cat([p.float() for p in parts]).contiguous()
+            self._packed_key = key
+        return self._packed
+
+    @torch.no_grad()
+    def fused_q(self, x: torch.Tensor) -> torch.Tensor:
+        """Q-values through the fused HIP forward (torch.ops.ttrl.mlp_q): inference only."""
+        from . import ops
+        widths, n_actions, dueling = self.fused_spec()
+        return ops.T.mlp_q(x.float(), self.packed_weights(), widths, n_actions, dueling)
+
+
+class MultiLayerPerceptron(_FusedMlp, nn.Module):
+    def __init__(self, inp: int, layers, out: int | None = None, reshape: bool = False, activation: str = "RELU"):
         super().__init__()
         sizes = [inp] + list(layers)
         self.layers = nn.ModuleList([nn.Linear(sizes[i], sizes[i + 1]) for i in range(len(sizes) - 1)])
         self.predict = nn.Linear(sizes[-1], out) if out else None
         self.reshape = reshape
+        self.activation_type = activation
+        self.activation = activation_factory(activation)
 
     def forward(self, x):
         if self.reshape:
             x = x.reshape(x.shape[0], -1)
         for layer in self.layers:
-            x = F.relu(layer(x))
+            x = self.activation(layer(x))
         return self.predict(x) if self.predict is not None else x
+
+    def _fused_parts(self):
+        return list(self.layers), [self.predict], False
+
+    def fused_supported(self) -> bool:
+        return (self.activation_type == "RELU" and self.predict is not None
+                and _mlp_in_kernel_domain(self.layers, self.predict.out_features))
+
+
+class DuelingNetwork(_FusedMlp, nn.Module):
+    """models.py:79-104: q = value + advantage - mean(advantage) over a shared base module."""
+
+    def __init__(self, inp: int, out: int, config: dict | None = None):
+        super().__init__()
+        c = config or {}
+        base, value, adv = (dict(c.get(k) or {}) for k in ("base_module", "value", "advantage"))
+        self.base_module = _mlp_from_config(base, inp, None)
+        last = self.base_module.layers[-1].out_features if len(self.base_module.layers) else inp
+        self.value = _mlp_from_config({"layers": [], **value}, last, 1)
+        self.advantage = _mlp_from_config({"layers": [], **adv}, last, out)
+        self.out = out
+
+    def forward(self, x):
+        x = self.base_module(x)
+        value = self.value(x).expand(-1, self.out)
+        advantage = self.advantage(x)
+        return value + advantage - advantage.mean(1).unsqueeze(1).expand(-1, self.out)
+
+    def _fused_parts(self):
+        return list(self.base_module.layers), [self.advantage.predict, self.value.predict], True
+
+    def fused_supported(self) -> bool:
+        return (self.base_module.activation_type == "RELU" and len(self.value.layers) == 0
+                and len(self.advantage.layers) == 0
+                and _mlp_in_kernel_domain(self.base_module.layers, self.out + 1))
+
+
+class ConvolutionalNetwork(nn.Module):
+    """models.py:107-154: three 2x2 stride-2 convolutions over a CHW observation and an MLP head.
+    It runs as torch kernels (12 k parameters, not on a measured hot path): never fused."""
+
+    def __init__(self, obs_shape, out: int, config: dict | None = None):
+        super().__init__()
+        c = config or {}
+        channels, height, width = (int(v) for v in obs_shape)
+        self.activation = activation_factory(c.get("activation", "RELU"))
+        self.conv1 = nn.Conv2d(channels, 16, kernel_size=2, stride=2)
+        self.conv2 = nn.Conv2d(16, 32, kernel_size=2, stride=2)
+        self.conv3 = nn.Conv2d(32, 64, kernel_size=2, stride=2)
+
+        def size_out(size, kernel_size=2, stride=2):
+            return (size - (kernel_size - 1) - 1) // stride + 1
+
+        convw, convh = size_out(size_out(size_out(width))), size_out(size_out(size_out(height)))
+        if convw <= 0 or convh <= 0:
+            raise ValueError(f"a {height} x {width} observation is too small for three stride-2 convolutions")
+        self.head = _mlp_from_config({"layers": [], **dict(c.get("head_mlp") or {})}, convw * convh * 64, out)
+
+    def reset(self, generator: torch.Generator | None = None):
+        return xavier_reset(self, generator)
+
+    def fused_supported(self) -> bool:
+        return False
+
+    def forward(self, x):
+        x = self.activation(self.conv1(x))
+        x = self.activation(self.conv2(x))
+        x = self.activation(self.conv3(x))
+        return self.head(x)
+
+
+def _mlp_from_config(c: dict, inp: int, out: int | None) -> MultiLayerPerceptron:
+    """MultiLayerPerceptron.default_config (models.py:62-67): layers [64, 64], RELU, reshape."""
+    return MultiLayerPerceptron(inp, c.get("layers", [64, 64]), out=out, reshape=bool(c.get("reshape", True)),
+                                activation=c.get("activation", "RELU"))
+
+
+def model_factory(config: dict, obs_shape, n_actions: int) -> nn.Module:
+    """models.model_factory (models.py:431-441) on a config sized as size_model_config does
+    (:404-428): ``in`` = prod(obs_shape), CHW for the convolutional net, ``out`` = n_actions."""
+    kind = config.get("type")
+    obs_shape = tuple(int(v) for v in obs_shape)
+    if kind == "MultiLayerPerceptron":
+        return _mlp_from_config(config, math.prod(obs_shape), n_actions)
+    if kind == "DuelingNetwork":
+        return DuelingNetwork(math.prod(obs_shape), n_actions, config)
+    if kind == "ConvolutionalNetwork":
+        return ConvolutionalNetwork(obs_shape, n_actions, config)
+    if kind == "EgoAttentionNetwork":
+        return EgoAttentionNetwork(n_actions, {**EGO_ATTENTION_2H, **config})
+    raise ValueError("Unknown model type")
 
 
 class EgoAttention(nn.Module):
@@ -139,11 +303,12 @@ class EgoAttentionNetwork(nn.Module):
         return self.output_layer(att)
 
 
-class EgoAttentionPolicy:
-    """Batched DQN acting: Q = value_net(obs[E, V, F]); epsilon-greedy on the device."""
+class _EpsilonGreedyPolicy:
+    """Batched DQN acting: Q = value_net(obs); epsilon-greedy on the device.  Subclasses build the
+    value net and name their fused acting operator (``_fused_act``)."""
 
-    def __init__(self, device, n_actions: int = 5, seed: int = 0, tau: float = 15000.0, temperature: float = 1.0,
-                 final_temperature: float = 0.05, fused: bool = True, env_id_offset: int = 0):
+    def __init__(self, device, value_net: nn.Module, n_actions: int, seed: int, tau: float, temperature: float,
+                 final_temperature: float, fused: bool, env_id_offset: int):
         self.device = torch.device(device)
         # the global env id of obs row 0 (a data-parallel rank's shard offset, sharding.shard): the
         # fused draws are keyed on the global env, so every shard of one seed explores independently
@@ -152,7 +317,7 @@ class EgoAttentionPolicy:
         self.fused = fused  # acting through the fused HIP forward on a GPU (training uses the torch graph)
         g = torch.Generator(device="cpu")
         g.manual_seed(seed)
-        self.value_net = EgoAttentionNetwork(n_actions).reset(g).to(self.device).eval()
+        self.value_net = value_net.reset(g).to(self.device).eval()
         self.n_actions = n_actions
         self.tau, self.t0, self.t1 = tau, temperature, final_temperature
         self.gen = torch.Generator(device=self.device)
@@ -186,19 +351,15 @@ class EgoAttentionPolicy:
         every replay.  ``dtype``: the actions' index type (int64, or int32 -- the env's own, which
         env.step takes without a cast launch).
 
-        On a GPU the forward, argmax and draw are ONE launch (ttrl::ego_attention_act, Philox
-        keyed on (seed, env_id_offset + row, step)); elsewhere the torch forward with torch's generator."""
+        On a GPU the forward, argmax and draw are ONE launch (ttrl::ego_attention_act or ttrl::mlp_act,
+        Philox keyed on (seed, env_id_offset + row, step)); elsewhere, and for a network the fused
+        forward does not cover, the torch forward with torch's generator."""
         t = self.time if t is None else int(t)
         self.time = t + 1
         self.last_epsilon = self.epsilon(self.time) if epsilon is None else epsilon
         if self.fused_acting(obs):
-            from . import ops
-            net = self.value_net
-            act, _ = ops.T.ego_attention_act(obs.float(), net.packed_weights(), net.attention_layer.h,
-                                             net.output_layer.predict.out_features,
-                                             self.last_epsilon if epsilon is None else 0.0, self.seed, self.time,
-                                             epsilon, step, int32_actions=dtype == torch.int32,
-                                             env_offset=self.env_id_offset)
+            act = self._fused_act(obs, self.last_epsilon if epsilon is None else 0.0, epsilon, step,
+                                  dtype == torch.int32)
             return act if act.dtype == dtype else act.to(dtype)
         epsilon = self.last_epsilon
         q = self.value_net(obs)
@@ -207,3 +368,44 @@ class EgoAttentionPolicy:
         u = torch.rand(e, device=self.device, generator=self.gen)
         rnd = torch.randint(0, self.n_actions, (e,), device=self.device, generator=self.gen)
         return torch.where(u < epsilon, rnd, greedy).to(dtype)
+
+
+class EgoAttentionPolicy(_EpsilonGreedyPolicy):
+    """Acting with the EgoAttention value net on obs[E, V, F]."""
+
+    def __init__(self, device, n_actions: int = 5, seed: int = 0, tau: float = 15000.0, temperature: float = 1.0,
+                 final_temperature: float = 0.05, fused: bool = True, env_id_offset: int = 0):
+        super().__init__(device, EgoAttentionNetwork(n_actions), n_actions, seed, tau, temperature, final_temperature,
+                         fused, env_id_offset)
+
+    def _fused_act(self, obs, eps, epsilon_dev, step_dev, int32_actions):
+        from . import ops
+        net = self.value_net
+        act, _ = ops.T.ego_attention_act(obs.float(), net.packed_weights(), net.attention_layer.h,
+                                         net.output_layer.predict.out_features, eps, self.seed, self.time,
+                                         epsilon_dev, step_dev, int32_actions=int32_actions,
+                                         env_offset=self.env_id_offset)
+        return act
+
+
+class QNetworkPolicy(_EpsilonGreedyPolicy):
+    """Acting with the value net ``model_factory`` builds from ``model`` (an agent config's "model"
+    dict) on obs[E, *obs_shape].  A MultiLayerPerceptron or DuelingNetwork inside the fused
+    forward's domain (``fused_supported``) acts through ttrl::mlp_act on a GPU, unless ``fused`` is
+    False; every other network acts through the torch path."""
+
+    def __init__(self, device, model: dict, obs_shape, n_actions: int = 5, seed: int = 0, tau: float = 15000.0,
+                 temperature: float = 1.0, final_temperature: float = 0.05, fused: bool = True,
+                 env_id_offset: int = 0):
+        self.obs_shape = tuple(int(v) for v in obs_shape)
+        super().__init__(device, model_factory(model, self.obs_shape, n_actions), n_actions, seed, tau, temperature,
+                         final_temperature, fused, env_id_offset)
+
+    def _fused_act(self, obs, eps, epsilon_dev, step_dev, int32_actions):
+        from . import ops
+        net = self.value_net
+        widths, n_actions, dueling = net.fused_spec()
+        act, _ = ops.T.mlp_act(obs.float(), net.packed_weights(), widths, n_actions, dueling, eps, self.seed,
+                               self.time, epsilon_dev, step_dev, int32_actions=int32_actions,
+                               env_offset=self.env_id_offset)
+        return act

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "ttrl_mi355x.h"
+#include "ttrl_qnet.h"
 
 namespace {
 
@@ -494,9 +495,266 @@ int forward(const float* obs, int32_t batch, int32_t n_entities, int32_t n_featu
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Fused MultiLayerPerceptron / DuelingNetwork Q-value forward with the same acting epilogue
+// (models.py:50-104; baseline.json [128, 128] on the flattened Kinematics rows, grid.json [48, 48]
+// on the flattened OccupancyGrid).  Packed weights: include/ttrl_qnet.h.
+struct MlpNet {
+  int in, n_layers, w0, w1, w2, A, dueling;
+};
+__host__ __device__ inline int mlp_width(const MlpNet& n, int l) { return l == 0 ? n.w0 : (l == 1 ? n.w1 : n.w2); }
+__host__ __device__ inline int mlp_head_cols(const MlpNet& n) { return n.A + (n.dueling ? 1 : 0); }
+__host__ __device__ inline long mlp_packed_floats(const MlpNet& n) {
+  long p = 0;
+  int k = n.in;
+  for (int l = 0; l < n.n_layers; ++l) {
+    p += (long)(k + 1) * mlp_width(n, l);
+    k = mlp_width(n, l);
+  }
+  return p + (long)(k + 1) * mlp_head_cols(n);
+}
+
+constexpr int MLP_ROWS = 16;   // envs per workgroup: one MFMA tile of rows
+constexpr int MLP_WAVES = 4;   // each takes a quarter of every layer's k steps
+constexpr int MLP_KC = 512;    // observation columns staged in LDS at a time
+constexpr int MLP_QS = 17;     // row stride of the head's Q rows in LDS
+
+// LDS of one workgroup (floats).  Every row stride is 2 x an odd number, so the 16 rows of an A
+// operand read (lane l: row l & 15, column k + (l >> 4)) fall on 32 different banks.
+//   [0, h)      the staged observation chunk [16][sx], then the waves' partial sums [4][16][sp]
+//   [h, q)      the activations between two layers [16][sp]
+//   [q, total)  the head's outputs [16][MLP_QS]
+struct MlpLds {
+  int sx, sp, h, q, total;
+};
+__host__ __device__ inline MlpLds mlp_lds(const MlpNet& n) {
+  MlpLds P;
+  int wmax = 16;
+  for (int l = 0; l < n.n_layers; ++l) wmax = mlp_width(n, l) > wmax ? mlp_width(n, l) : wmax;
+  const int in4 = (n.in + 3) & ~3;
+  P.sx = (in4 < MLP_KC ? in4 : MLP_KC) + 2;
+  P.sp = wmax + 2;
+  const int x = MLP_ROWS * P.sx, parts = MLP_WAVES * MLP_ROWS * P.sp;
+  P.h = x > parts ? x : parts;
+  P.q = P.h + MLP_ROWS * P.sp;
+  P.total = P.q + MLP_ROWS * MLP_QS;
+  return P;
+}
+
+// One layer's partial sums: out[16 envs][N] = in[16][K] Wt[K][N] with the k steps (4 inputs each)
+// split over the workgroup's waves, each wave over all NT = ceil(N / 16) output tiles: any tile
+// count keeps the four waves busy (three tiles at width 48 would idle one of four tile-owning
+// waves through the 212 k steps of an 847-wide grid row), the A operand is read from LDS once per
+// k step for all tiles, and every weight is read from L2 once per workgroup, straight into the B
+// operand (k rows of 16 consecutive floats).  The first layer's input is staged from HBM in chunks
+// of MLP_KC columns, rows read along `in` (coalesced; the row stride needs no alignment), zero
+// beyond `in` and beyond the batch; the others read the activations the reduction left in LDS.
+// The partials go to lds[(wave * 16 + env) * sp + col].
+// U consecutive k steps from step s on: every operand is requested before the first MFMA, so one
+// L2 latency covers U x NT weight loads.
+template <int NT, int U>
+__device__ __forceinline__ void mlp_steps(const float* xrow, int s, int c0, int K, const float* __restrict__ Wt, int N,
+                                          const int (&col)[NT], int g, int c, f32x4 (&acc)[NT]) {
+  float a[U], b[U][NT];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int kl = 4 * (s + u) + g, k = c0 + kl;
+    a[u] = xrow[kl];
+    const float* wr = Wt + (long)(k < K ? k : K - 1) * N;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) b[u][t] = wr[col[t]];
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const bool kv = c0 + 4 * (s + u) + g < K;  // the last step's inputs beyond K are zero columns
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = mfma4(a[u], kv && 16 * t + c < N ? b[u][t] : 0.0f, acc[t]);
+  }
+}
+
+template <int NT>
+__device__ __forceinline__ void mlp_partials(const float* __restrict__ obs, int B, long b0, int K, bool first,
+                                             float* lds, const MlpLds& P, const float* __restrict__ Wt, int N) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: the k loops stay scalar
+  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+  const int S = first ? P.sx : P.sp;
+  const float* xrow = (first ? lds : lds + P.h) + c * S;
+  f32x4 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  int col[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) col[t] = 16 * t + c < N ? 16 * t + c : N - 1;  // the head's tile is partial
+  for (int c0 = 0; c0 < K; c0 += MLP_KC) {
+    const int kc = K - c0 < MLP_KC ? K - c0 : MLP_KC, kc4 = (kc + 3) & ~3;
+    if (first) {
+      constexpr int RPW = MLP_ROWS / MLP_WAVES;  // rows staged per wave, 64 columns of each per pass
+      __syncthreads();  // the previous chunk has been consumed
+      for (int i0 = 0; i0 < kc4; i0 += 64) {
+        const int i = i0 + lane;
+        float v[RPW];
+#pragma unroll
+        for (int j = 0; j < RPW; ++j) {
+          const bool live = b0 + wave * RPW + j < B && i < kc;
+          const float x = obs[(live ? b0 + wave * RPW + j : b0) * (long)K + c0 + (live ? i : 0)];
+          v[j] = live ? x : 0.0f;
+        }
+        if (i < kc4) {
+#pragma unroll
+          for (int j = 0; j < RPW; ++j) lds[(wave * RPW + j) * S + i] = v[j];
+        }
+      }
+      __syncthreads();
+    }
+    const int ns = kc4 / 4, s1 = (wave + 1) * ns / MLP_WAVES;
+    int s = wave * ns / MLP_WAVES;
+    for (; s + 4 <= s1; s += 4) mlp_steps<NT, 4>(xrow, s, c0, K, Wt, N, col, g, c, acc);
+    for (; s < s1; ++s) mlp_steps<NT, 1>(xrow, s, c0, K, Wt, N, col, g, c, acc);
+  }
+  __syncthreads();  // every wave is done with the layer's input: the partials overlay the staged chunk
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lds[(wave * MLP_ROWS + 4 * g + r) * P.sp + 16 * t + c] = acc[t][r];
+  __syncthreads();
+}
+
+__device__ __forceinline__ void mlp_layer(int tiles, const float* __restrict__ obs, int B, long b0, int K, bool first,
+                                          float* lds, const MlpLds& P, const float* __restrict__ Wt, int N) {
+  switch (tiles) {
+    case 1: mlp_partials<1>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    case 2: mlp_partials<2>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    case 3: mlp_partials<3>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    case 4: mlp_partials<4>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    case 5: mlp_partials<5>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    case 6: mlp_partials<6>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    case 7: mlp_partials<7>(obs, B, b0, K, first, lds, P, Wt, N); break;
+    default: mlp_partials<8>(obs, B, b0, K, first, lds, P, Wt, N); break;
+  }
+}
+
+// dst[env][col] = sum of the four waves' partials + bias, ReLU'd between layers (a NaN stays a NaN,
+// as in F.relu).  Thread i: env i & 15, column i >> 4 (+ 16 per pass): conflict-free on both sides.
+__device__ __forceinline__ void mlp_reduce(const float* parts, int sp, const float* __restrict__ bias, int N,
+                                           float* dst, int ds, bool relu) {
+  const int ws = MLP_ROWS * sp;  // one wave's partials
+  for (int i = threadIdx.x; i < MLP_ROWS * N; i += 64 * MLP_WAVES) {
+    const int row = i & (MLP_ROWS - 1), cl = i >> 4;
+    const float* p = parts + row * sp + cl;
+    float v = ((p[0] + p[ws]) + (p[2 * ws] + p[3 * ws])) + bias[cl];
+    if (relu) v = v < 0.0f ? 0.0f : v;
+    dst[row * ds + cl] = v;
+  }
+  __syncthreads();
+}
+
+// One workgroup of four waves per 16 envs.  Only Q (and the actions) reach HBM.
+__global__ void __launch_bounds__(64 * MLP_WAVES) mlp_q_kernel(const float* __restrict__ obs, int B, MlpNet net,
+                                                               const float* __restrict__ W, float* __restrict__ Q,
+                                                               Explore ex) {
+  extern __shared__ float4 lds4[];
+  float* lds = reinterpret_cast<float*>(lds4);
+  const MlpLds P = mlp_lds(net);
+  const long b0 = (long)blockIdx.x * MLP_ROWS;
+  const int A = net.A;
+  int K = net.in;
+  const float* w = W;
+  for (int l = 0; l < net.n_layers; ++l) {
+    const int N = mlp_width(net, l);
+    mlp_layer(N >> 4, obs, B, b0, K, l == 0, lds, P, w, N);
+    mlp_reduce(lds, P.sp, w + (long)K * N, N, lds + P.h, P.sp, true);
+    w += (long)(K + 1) * N;
+    K = N;
+  }
+  // the head: predict [K][A], or advantage.predict and value.predict as one [K][A + 1] tile
+  const int NH = mlp_head_cols(net);
+  mlp_partials<1>(obs, B, b0, K, false, lds, P, w, NH);
+  mlp_reduce(lds, P.sp, w + (long)K * NH, NH, lds + P.q, MLP_QS, false);
+  const int k = threadIdx.x;
+  if (k < MLP_ROWS && b0 + k < B) {  // lane k: env b0 + k
+    float* qrow = lds + P.q + k * MLP_QS;
+    if (net.dueling) {  // value + advantage - mean(advantage), in that order (models.py:100-104)
+      float sum = 0.0f;
+      for (int i = 0; i < A; ++i) sum += qrow[i];
+      const float mean = sum / (float)A, value = qrow[A];
+      for (int i = 0; i < A; ++i) qrow[i] = (value + qrow[i]) - mean;
+    }
+    for (int i = 0; i < A; ++i) Q[(b0 + k) * A + i] = qrow[i];
+    if (ex.act || ex.act32) {  // epsilon-greedy, as step 4 of ego_attention_kernel
+      int best = 0;
+      float bq = qrow[0];
+      for (int i = 1; i < A; ++i) {
+        const float v = qrow[i];
+        if (bq == bq && (v > bq || v != v)) { bq = v; best = i; }  // np.argmax: first max, first NaN
+      }
+      const float eps = ex.eps_dev ? *ex.eps_dev : ex.eps;
+      const unsigned long long step = ex.step_dev ? (unsigned long long)*ex.step_dev : (unsigned long long)ex.step;
+      const unsigned long long env = (unsigned long long)ex.env_offset + (unsigned long long)(b0 + k);
+      const uint4 r = philox4x32(make_uint4((unsigned)env, (unsigned)(env >> 32), (unsigned)step, (unsigned)(step >> 32)),
+                                 make_uint2(ex.seed_lo, ex.seed_hi));
+      const float uni = (float)(r.x >> 8) * 0x1p-24f;                       // U[0, 1)
+      const int rnd = (int)(((unsigned long long)r.y * (unsigned)A) >> 32);  // U{0 .. A-1}
+      const int pick = uni < eps ? rnd : best;
+      if (ex.act) ex.act[b0 + k] = pick;
+      if (ex.act32) ex.act32[b0 + k] = pick;
+    }
+  }
+}
+
+// TTRL_OK and *net for a network inside the kernel's domain; TTRL_E_ARG for sizes that describe no
+// network, TTRL_E_UNSUPPORTED for one the kernel does not cover.
+int mlp_net(int32_t in, int32_t n_layers, const int32_t* widths, int32_t n_actions, int32_t dueling, MlpNet* net) {
+  if (!widths || in < 1 || n_layers < 1 || n_actions < 1 || (dueling != 0 && dueling != 1)) return TTRL_E_ARG;
+  for (int l = 0; l < n_layers && l < 3; ++l)
+    if (widths[l] < 1) return TTRL_E_ARG;
+  if (n_layers > 3 || in > 1024 || n_actions + dueling > 16) return TTRL_E_UNSUPPORTED;
+  for (int l = 0; l < n_layers; ++l)
+    if (widths[l] % 16 != 0 || widths[l] > 128) return TTRL_E_UNSUPPORTED;
+  *net = MlpNet{in, n_layers, widths[0], n_layers > 1 ? widths[1] : 0, n_layers > 2 ? widths[2] : 0, n_actions, dueling};
+  return TTRL_OK;
+}
+
+int mlp_forward(const float* obs, int32_t batch, int32_t in, int32_t n_layers, const int32_t* widths,
+                const float* weights, int32_t n_actions, int32_t dueling, float* q, const Explore& ex, void* stream) {
+  if (batch < 0) return TTRL_E_ARG;
+  MlpNet net;
+  const int rc = mlp_net(in, n_layers, widths, n_actions, dueling, &net);
+  if (rc != TTRL_OK) return rc;
+  if (batch == 0) return TTRL_OK;  // an empty batch has no rows to point at
+  if (!obs || !weights || !q) return TTRL_E_ARG;
+  const size_t lds = mlp_lds(net).total * sizeof(float);
+  hipLaunchKernelGGL(mlp_q_kernel, dim3((batch + MLP_ROWS - 1) / MLP_ROWS), dim3(64 * MLP_WAVES), lds,
+                     (hipStream_t)stream, obs, batch, net, weights, q, ex);
+  return hipGetLastError() == hipSuccess ? TTRL_OK : TTRL_E_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t ttrl_mlp_sizes(int32_t in, int32_t n_layers, const int32_t* widths, int32_t n_actions, int32_t dueling) {
+  MlpNet net;
+  const int rc = mlp_net(in, n_layers, widths, n_actions, dueling, &net);
+  return rc != TTRL_OK ? rc : mlp_packed_floats(net);
+}
+
+int ttrl_mlp_q(const float* obs, int32_t batch, int32_t in, int32_t n_layers, const int32_t* widths,
+               const float* weights, int32_t n_actions, int32_t dueling, float* q, void* stream) {
+  return mlp_forward(obs, batch, in, n_layers, widths, weights, n_actions, dueling, q, Explore{}, stream);
+}
+
+int ttrl_mlp_act(const float* obs, int32_t batch, int32_t in, int32_t n_layers, const int32_t* widths,
+                 const float* weights, int32_t n_actions, int32_t dueling, float epsilon, const float* epsilon_dev,
+                 uint64_t seed, int64_t step, const int64_t* step_dev, int64_t env_offset, float* q, int64_t* actions,
+                 int32_t* actions32, void* stream) {
+  if ((!actions && !actions32) || !(epsilon >= 0.0f && epsilon <= 1.0f) || env_offset < 0) return TTRL_E_ARG;
+  Explore ex{};
+  ex.env_offset = env_offset;
+  ex.act = actions; ex.act32 = actions32;
+  ex.eps = epsilon; ex.eps_dev = epsilon_dev; ex.step = step; ex.step_dev = step_dev;
+  ex.seed_lo = (unsigned)seed; ex.seed_hi = (unsigned)(seed >> 32);
+  return mlp_forward(obs, batch, in, n_layers, widths, weights, n_actions, dueling, q, ex, stream);
+}
 
 int64_t ttrl_ego_attention_sizes(int32_t n_features, int32_t n_actions, int32_t batch, int32_t n_entities,
                                  int64_t* scratch_floats) {

@@ -20,8 +20,10 @@
 
 #include <cstddef>
 #include <cstring>
+#include <vector>
 
 #include "ttrl_mi355x.h"
+#include "ttrl_qnet.h"
 
 namespace {
 
@@ -676,6 +678,74 @@ std::tuple<at::Tensor, at::Tensor> ego_attention_act(const at::Tensor& obs, cons
   return {act, q};
 }
 
+// The fused MLP / dueling Q-network (ttrl_qnet.h).  obs [B, ...] of any rank is flattened: `in` is
+// the product of the remaining dimensions.
+struct MlpArgs {
+  at::Tensor x;
+  int32_t B, in;
+  std::vector<int32_t> widths;
+};
+MlpArgs mlp_args(const at::Tensor& obs, const at::Tensor& weights, at::IntArrayRef widths, int64_t n_actions,
+                 bool dueling) {
+  check_hip(obs);
+  TORCH_CHECK(obs.dim() >= 1 && obs.scalar_type() == at::kFloat, "ttrl: obs must be float32 [B, ...]");
+  TORCH_CHECK(weights.device() == obs.device() && weights.scalar_type() == at::kFloat && weights.is_contiguous(),
+              "ttrl: weights must be a contiguous float32 tensor on the obs device (packed layout)");
+  MlpArgs a;
+  a.x = obs.contiguous();
+  a.B = static_cast<int32_t>(obs.size(0));
+  int64_t in = 1;
+  for (int64_t d = 1; d < obs.dim(); ++d) in *= obs.size(d);
+  a.in = static_cast<int32_t>(in);
+  for (int64_t w : widths) a.widths.push_back(static_cast<int32_t>(w));
+  const int64_t n_w = ttrl_mlp_sizes(a.in, static_cast<int32_t>(a.widths.size()), a.widths.data(),
+                                     static_cast<int32_t>(n_actions), dueling);
+  TORCH_CHECK(n_w > 0, "ttrl: the fused MLP forward does not cover this network (in ", in, ", ", widths.size(),
+              " layers, ", n_actions, " actions): ", n_w == TTRL_E_ARG ? "TTRL_E_ARG" : "TTRL_E_UNSUPPORTED");
+  TORCH_CHECK(weights.numel() == n_w, "ttrl: packed weights need ", n_w, " floats, got ", weights.numel());
+  return a;
+}
+
+at::Tensor mlp_q(const at::Tensor& obs, const at::Tensor& weights, at::IntArrayRef widths, int64_t n_actions,
+                 bool dueling) {
+  const MlpArgs a = mlp_args(obs, weights, widths, n_actions, dueling);
+  at::Tensor q = at::empty({a.B, n_actions}, opts(a.x, at::kFloat));
+  ok(ttrl_mlp_q(a.x.data_ptr<float>(), a.B, a.in, static_cast<int32_t>(a.widths.size()), a.widths.data(),
+                weights.data_ptr<float>(), static_cast<int32_t>(n_actions), dueling, q.data_ptr<float>(),
+                stream_of(a.x)),
+     "ttrl_mlp_q");
+  return q;
+}
+
+// (actions, q) as ego_attention_act, through ttrl_mlp_act.
+std::tuple<at::Tensor, at::Tensor> mlp_act(const at::Tensor& obs, const at::Tensor& weights, at::IntArrayRef widths,
+                                           int64_t n_actions, bool dueling, double epsilon, int64_t seed, int64_t step,
+                                           const c10::optional<at::Tensor>& epsilon_dev,
+                                           const c10::optional<at::Tensor>& step_dev, bool int32_actions,
+                                           int64_t env_offset) {
+  const MlpArgs a = mlp_args(obs, weights, widths, n_actions, dueling);
+  TORCH_CHECK(epsilon >= 0.0 && epsilon <= 1.0, "ttrl: epsilon must lie in [0, 1]");
+  TORCH_CHECK(env_offset >= 0, "ttrl: env_offset must be non-negative");
+  const bool ed = epsilon_dev && epsilon_dev->defined(), sd = step_dev && step_dev->defined();
+  if (ed)
+    TORCH_CHECK(epsilon_dev->device() == obs.device() && epsilon_dev->scalar_type() == at::kFloat &&
+                    epsilon_dev->numel() == 1,
+                "ttrl: epsilon_dev must be a float32 scalar on the obs device");
+  if (sd)
+    TORCH_CHECK(step_dev->device() == obs.device() && step_dev->scalar_type() == at::kLong && step_dev->numel() == 1,
+                "ttrl: step_dev must be an int64 scalar on the obs device");
+  at::Tensor q = at::empty({a.B, n_actions}, opts(a.x, at::kFloat));
+  at::Tensor act = at::empty({a.B}, opts(a.x, int32_actions ? at::kInt : at::kLong));
+  ok(ttrl_mlp_act(a.x.data_ptr<float>(), a.B, a.in, static_cast<int32_t>(a.widths.size()), a.widths.data(),
+                  weights.data_ptr<float>(), static_cast<int32_t>(n_actions), dueling, static_cast<float>(epsilon),
+                  ed ? epsilon_dev->data_ptr<float>() : nullptr, static_cast<uint64_t>(seed), step,
+                  sd ? step_dev->data_ptr<int64_t>() : nullptr, env_offset, q.data_ptr<float>(),
+                  int32_actions ? nullptr : act.data_ptr<int64_t>(), int32_actions ? act.data_ptr<int32_t>() : nullptr,
+                  stream_of(a.x)),
+     "ttrl_mlp_act");
+  return {act, q};
+}
+
 // ------------------------------------------------------------------------------------ Meta kernels
 const at::Tensor& meta_x(at::TensorList ts) {
   TORCH_CHECK(ts.size() == kFields, "ttrl: state must hold ", kFields, " tensors in _abi.ALL_FIELDS order, got ",
@@ -804,6 +874,17 @@ std::tuple<at::Tensor, at::Tensor> meta_ego_attention_act(const at::Tensor& obs,
           at::empty({obs.size(0), n_actions}, opts(obs, at::kFloat))};
 }
 
+at::Tensor meta_mlp_q(const at::Tensor& obs, const at::Tensor&, at::IntArrayRef, int64_t n_actions, bool) {
+  return at::empty({obs.size(0), n_actions}, opts(obs, at::kFloat));
+}
+std::tuple<at::Tensor, at::Tensor> meta_mlp_act(const at::Tensor& obs, const at::Tensor&, at::IntArrayRef,
+                                                int64_t n_actions, bool, double, int64_t, int64_t,
+                                                const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
+                                                bool int32_actions, int64_t) {
+  return {at::empty({obs.size(0)}, opts(obs, int32_actions ? at::kInt : at::kLong)),
+          at::empty({obs.size(0), n_actions}, opts(obs, at::kFloat))};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(ttrl, m) {
@@ -852,6 +933,10 @@ TORCH_LIBRARY(ttrl, m) {
   m.def("ego_attention_q(Tensor obs, Tensor weights, int heads, int n_actions) -> Tensor");
   m.def("ego_attention_act(Tensor obs, Tensor weights, int heads, int n_actions, float epsilon, int seed, int step, "
         "Tensor? epsilon_dev=None, Tensor? step_dev=None, bool int32_actions=False, int env_offset=0) -> (Tensor, Tensor)");
+  m.def("mlp_q(Tensor obs, Tensor weights, int[] widths, int n_actions, bool dueling) -> Tensor");
+  m.def("mlp_act(Tensor obs, Tensor weights, int[] widths, int n_actions, bool dueling, float epsilon, int seed, "
+        "int step, Tensor? epsilon_dev=None, Tensor? step_dev=None, bool int32_actions=False, int env_offset=0) -> "
+        "(Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(ttrl, CUDA, m) {  // the HIP device of ROCm PyTorch
@@ -880,6 +965,8 @@ TORCH_LIBRARY_IMPL(ttrl, CUDA, m) {  // the HIP device of ROCm PyTorch
   m.impl("rewards_step_", &rewards_step_);
   m.impl("ego_attention_q", &ego_attention_q);
   m.impl("ego_attention_act", &ego_attention_act);
+  m.impl("mlp_q", &mlp_q);
+  m.impl("mlp_act", &mlp_act);
 }
 
 TORCH_LIBRARY_IMPL(ttrl, Meta, m) {
@@ -908,4 +995,6 @@ TORCH_LIBRARY_IMPL(ttrl, Meta, m) {
   m.impl("rewards_step_", &meta_rewards_step);
   m.impl("ego_attention_q", &meta_ego_attention);
   m.impl("ego_attention_act", &meta_ego_attention_act);
+  m.impl("mlp_q", &meta_mlp_q);
+  m.impl("mlp_act", &meta_mlp_act);
 }

@@ -21,8 +21,8 @@ import torch
 
 class StepGraph:
     """``replay()`` advances every env by one policy step; returns (obs, reward, terminated,
-    truncated) static tensors.  ``policy``: an ``EgoAttentionPolicy`` (actions from the current
-    observation) or None (then ``actions`` [steps?, E] device tensor rows are consumed in order
+    truncated) static tensors.  ``policy``: an ``EgoAttentionPolicy`` or a ``QNetworkPolicy`` (actions
+    from the current observation: ``act(obs, epsilon=, step=, dtype=)``, ``epsilon(t)``, ``time``, ``gen``) or None (then ``actions`` [steps?, E] device tensor rows are consumed in order
     from a static buffer the caller fills via ``set_actions``)."""
 
     def __init__(self, env, obs: torch.Tensor, policy=None, warmup: int = 2):

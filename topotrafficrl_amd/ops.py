@@ -27,6 +27,7 @@ OPS = ["simulate_", "road_act_", "road_step_", "meta_action_", "env_step_", "nei
        "kinematics_obs_masked_", "occupancy_grid", "observe_ttc", "observe_lidar", "reset_highway_",
        "reset_highway_seeded_", "auto_reset_highway_", "ix_reset_", "ix_reset_parts_", "ix_clear_spawn_", "ix_step_tail_", "ix_env_step_", "copy_envs_", "rewards", "rewards_ex",
        "rewards_step_", "ego_attention_q", "ego_attention_act"]
+QNET_OPS = ["mlp_q", "mlp_act"]  # include/ttrl_qnet.h: the fused MLP / dueling Q-network forward and acting
 
 _loaded = False
 

@@ -20,7 +20,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from .agent import EgoAttentionPolicy
+from .agent import EgoAttentionPolicy, QNetworkPolicy
 from .dqn import DEFAULT_CONFIG, DQNLearner
 
 logger = logging.getLogger(__name__)
@@ -28,16 +28,41 @@ logger = logging.getLogger(__name__)
 
 class BatchedDQNAgent:
     """DQNAgent (deep_q_network/pytorch.py, abstract.py) for batched observations: acting with
-    the EgoAttention-2h value net and epsilon-greedy exploration, learning with the batched
-    replay memory / double-DQN residual / Adam / target sync of ``dqn.DQNLearner``."""
+    the config's value net and epsilon-greedy exploration, learning with the batched replay
+    memory / double-DQN residual / Adam / target sync of ``dqn.DQNLearner``.
 
-    def __init__(self, device, n_actions: int = 5, seed: int = 0, config: dict | None = None, env_id_offset: int = 0):
-        self.policy = EgoAttentionPolicy(device, n_actions=n_actions, seed=seed, env_id_offset=env_id_offset)
+    ``config["model"]``: the reference's model config (agent.model_factory).  Without one, or with
+    type "EgoAttentionNetwork", the agent acts with the EgoAttention-2h net; any other type
+    (MultiLayerPerceptron, DuelingNetwork, ConvolutionalNetwork) builds a ``QNetworkPolicy`` and
+    needs ``obs_shape``, the env's observation shape."""
+
+    def __init__(self, device, n_actions: int = 5, seed: int = 0, config: dict | None = None, env_id_offset: int = 0,
+                 obs_shape=None):
+        model = (config or {}).get("model")
+        if model is None or model.get("type") == "EgoAttentionNetwork":
+            self.policy = EgoAttentionPolicy(device, n_actions=n_actions, seed=seed, env_id_offset=env_id_offset)
+        else:
+            if obs_shape is None:
+                raise ValueError(f"a {model.get('type')} model needs obs_shape (the env's observation_space.shape)")
+            ex = (config or {}).get("exploration") or {}  # EpsilonGreedy's schedule (epsilon_greedy.py:11-14)
+            self.policy = QNetworkPolicy(device, model, obs_shape, n_actions=n_actions, seed=seed,
+                                         tau=ex.get("tau", 15000.0), temperature=ex.get("temperature", 1.0),
+                                         final_temperature=ex.get("final_temperature", 0.05),
+                                         env_id_offset=env_id_offset)
         self.config = {**DEFAULT_CONFIG, **(config or {})}
         self.seed_value = seed
         self.learner = None  # built on the first record (the observation shape is known then)
         self.training = True
         self.writer = None
+
+    @classmethod
+    def from_env(cls, env, config: dict | None = None, seed: int = 0):
+        """The agent for a batched env: its device, observation shape, action count and global env
+        ids (``env_id_offset``) are read from the env; ``config``: an agent config of the reference
+        (its JSON, base_config resolved), or None."""
+        return cls(env.device, n_actions=int(env.action_space.n), seed=seed, config=config,
+                   env_id_offset=int(env.config.get("env_id_offset", 0) or 0),
+                   obs_shape=tuple(env.observation_space.shape))
 
     def plan(self, observation):
         """AbstractAgent.plan: a sequence of actions whose first element is applied (batched: [E])."""
@@ -110,7 +135,7 @@ class BatchedEvaluation:
         self.observation = None
         if hasattr(agent, "set_writer"):
             agent.set_writer(writer)
-        if isinstance(getattr(agent, "policy", None), EgoAttentionPolicy) and hasattr(env, "config"):
+        if isinstance(getattr(agent, "policy", None), (EgoAttentionPolicy, QNetworkPolicy)) and hasattr(env, "config"):
             # the env's global ids (a data-parallel rank's shard): exploration keyed on them.  An
             # offset given to the agent explicitly is kept: an env left at offset 0 does not reset it,
             # and a different non-zero env offset is a conflict, not a silent override
